@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the walk-jump hot path: sampled conformations / second, whole job.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over the walker batch: one denoiser forward + the BAOAB state update + one saved
 frame for every walker (save_every_n_steps = 1), i.e. one conformation per walker per step — the unit the reference calls
@@ -22,11 +22,17 @@ default, as "f16x3": each fp32 operand split exactly into two f16 terms, three f
 the level of one fp32 rounding per product.  The reference's sampling precision is "32-true" and its bf16 mode is
 undefined, and the 1e-5 nm parity bar needs fp32-level accuracy.
 
-Timing: W untimed warm-up steps, then the K-step walk is timed R times back to back — each repeat bracketed by a barrier +
-torch.cuda.synchronize() on both sides and taken as the MAX over ranks — until >= ~10 s of timed work have accumulated
-(a 20-step walk lasts 20 ms, below what an external GPU-busy sampler resolves); ``ms_per_step`` and ``value`` are the
-MEDIAN repeat.  ``--repeats R`` fixes R.  The CPU baseline (rank 0, N = 1) runs FIRST, so that the GPU legs are the tail of
-the run and an outside observer sampling GPU activity sees them.
+Timing: W untimed warm-up steps, then ONE walk of exactly K steps is timed, bracketed by a barrier + torch.cuda.synchronize()
+on both sides and taken as the MAX over ranks; ``ms_per_step`` and ``value`` come from it.  ``--repeats R`` times the K-step
+walk R times back to back instead and reports the MEDIAN repeat; every repeat starts from the same post-warm-up state, so the
+last computes what the first did.  ``--dump-outputs DIR`` then writes what the last timed step returned (``dump_outputs``).
+
+A plain run does only that.  ``--full`` adds everything else, as every run did before the option existed: HIP events around
+the dominant kernel inside the timed region and the roofline / per-kernel figures built from them, repeats until >= ~10 s of
+timed work when ``--repeats`` is not given (a 20-step walk lasts 20 ms, below what an external GPU-busy sampler resolves), the
+CPU baseline (rank 0, N = 1; it runs FIRST, so that the GPU legs are the tail of the run and an outside observer sampling GPU
+activity sees them), the ``also`` / ``e2e`` / ``batch_sweep`` / ``secondary_rooflines`` legs, the ``rccl`` record and, for
+N > 1, the ``e2e_sharded`` leg.  The ``--no-*`` switches trim a ``--full`` run.
 
 Multi-GPU: one process per GPU.  Either launch with ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``
 or just ``python bench.py --gpus N``: without WORLD_SIZE in the environment the parent spawns the N ranks itself (before any
@@ -84,6 +90,31 @@ def workload_molecules(cfg: str, walkers: int, atoms=None, rank: int = 0):
     kinds = [synth.random_chain(rng.randint(17, 57), seed=100 + i + 16 * rank) for i in range(8)]
     per = -(-walkers // len(kinds))
     return [m for m in kinds for _ in range(per)][:walkers]
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, seed: int = 0) -> dict:
+    """Writes ``arrays`` ({name: tensor with one row per atom}) as ``path/<name>.npy`` in float32.  When they exceed DUMP_MAX_BYTES in
+    all, the same seeded sample of rows is kept of every array and its row indices are written as ``rows.npy`` (float64), so that
+    two builds run with the same arguments can still be compared output for output.  Returns {name: shape written}."""
+    import numpy as np
+
+    host = {k: t.detach().float().cpu().numpy() for k, t in arrays.items()}
+    n = {a.shape[0] for a in host.values()}
+    assert len(n) == 1, {k: a.shape for k, a in host.items()}
+    n = n.pop()
+    per_row = sum(a.nbytes for a in host.values()) // max(n, 1)
+    if per_row * n > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (per_row + 8)
+        rows = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        host = {k: np.ascontiguousarray(a[rows]) for k, a in host.items()}
+        host["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in host.items()}
 
 
 # ---- CPU baseline (rank 0, N = 1 only) ---------------------------------------------------------------------------------
@@ -613,7 +644,9 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="cfg2", help="workload (default: cfg2 = BASELINE configs[1], the metric's config)")
     ap.add_argument("--walkers", type=int, default=None, help="walkers per GPU (default: the config's)")
     ap.add_argument("--atoms", type=int, default=None, help="atoms per walker (default: the config's)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of the K-step walk (default: until >= 10 s)")
+    ap.add_argument("--repeats", type=int, default=0, help="timed repeats of the K-step walk (default: 1; with --full: until >= 10 s)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline as well (module docstring); the --no-* switches trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step returned (rank 0's walkers) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cfg1-cpu", action="store_true", help="skip the exact configs[0] CPU run (~1 min) inside cpu_baseline")
     ap.add_argument("--no-secondary", action="store_true", help="skip the scatter-mean / Langevin-kernel bandwidth measurements")
@@ -644,11 +677,12 @@ def main():
         if world > 1:
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         cpu = torch.device("cpu")
-        sharded = e2e_sharded(_StubModel(cpu), args.config, cpu, world, rank, steps=8, num_batches=2, walkers_total=3 * world + 1, stub=True)
-        rec = rccl_record(cpu, world)
+        line = {"metric": "dry-run", "value": 0.0, "n_gpus": world, "ranks_seen": int(t.item()), "steps": args.steps, "warmup": args.warmup}
+        if args.full:
+            line["e2e_sharded"] = e2e_sharded(_StubModel(cpu), args.config, cpu, world, rank, steps=8, num_batches=2, walkers_total=3 * world + 1, stub=True)
+            line["rccl"] = rccl_record(cpu, world)
         if rank == 0:
-            print(json.dumps({"metric": "dry-run", "value": 0.0, "n_gpus": world, "ranks_seen": int(t.item()), "steps": args.steps, "warmup": args.warmup,
-                              "e2e_sharded": sharded, "rccl": rec}), flush=True)
+            print(json.dumps(line), flush=True)
         if world > 1:
             torch.distributed.destroy_process_group()
         return
@@ -667,7 +701,7 @@ def main():
 
     cfg = CONFIGS[args.config]
     cpu_line = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_line = cpu_baseline(args.config, cfg1_exact=not args.no_cfg1_cpu)  # before the GPU legs (see the module docstring)
     walkers = args.walkers if args.walkers is not None else cfg["walkers"]
     total_walkers = None
@@ -700,6 +734,8 @@ def main():
         return smp.walk("baoab", y, v, params, None, seed=1234 + rank, save_trajectory=True)
 
     def timed(steps, profile):
+        y.copy_(y_start)  # (the walk updates y and v in place: every repeat starts from the same state)
+        v.copy_(v_start)
         torch.cuda.synchronize()
         dist.barrier()
         torch.cuda.synchronize()
@@ -711,31 +747,43 @@ def main():
 
     if args.warmup > 0:
         walk(args.warmup)
+    y_start, v_start = y.clone(), v.clone()
+    # the timed walk's output buffers once in front of the timed region: the caching allocator hands the same blocks to the walk
+    _bufs = [torch.empty(args.steps, n, 3, device=dev) for _ in range(3)] + [torch.empty(n, 3, device=dev)]
+    del _bufs
     # HIP events only around the dominant kernel inside the timed region (timing all 16 launches of a step costs ~4 %)
-    prof_mode = None if args.no_profile else "dominant"
+    prof_mode = "dominant" if args.full and not args.no_profile else None
     if prof_mode:
         # Every bracketed launch costs two event records (~3 % of the step with all five conv launches of a step timed): only the dominant
         # kernel, and every PROF_EVERY-th of its launches — coprime to the launches per step, so every layer is visited (same box: 277–285 k
         # with every launch timed, 287–290 k with every 7th, 293 k without events).  Armed ONCE, outside the timed region.
         smp.profile_enable(True, classes=["conv0", "conv1"], every=PROF_EVERY)
     dts = []
-    dt, (y_traj, score_traj, xhat_traj, xhat) = timed(args.steps, prof_mode)
-    assert xhat_traj.shape[0] == args.steps and torch.isfinite(xhat_traj).all()
+    dt, last = timed(args.steps, prof_mode)
+    assert last[2].shape[0] == args.steps and torch.isfinite(last[2]).all()
     dts.append(dt)
     prof = smp.profile_read() if prof_mode else None  # events of the first repeat (the pool is re-armed per repeat)
-    reps = args.repeats if args.repeats > 0 else None
-    t_first = torch.tensor([dt], dtype=torch.float64, device=dev)
-    if world > 1:
-        torch.distributed.all_reduce(t_first, op=torch.distributed.ReduceOp.MAX)
+    reps = args.repeats if args.repeats > 0 else None if args.full else 1
     if reps is None:  # the same count on every rank: derived from the max-over-ranks time of the first repeat
+        t_first = torch.tensor([dt], dtype=torch.float64, device=dev)
+        if world > 1:
+            torch.distributed.all_reduce(t_first, op=torch.distributed.ReduceOp.MAX)
         reps = int(min(5000, max(1, math.ceil(MIN_TIMED_S / max(float(t_first.item()), 1e-6)))))
     for it in range(reps - 1):
-        dt, _o = timed(args.steps, prof_mode)
+        last = None  # (the previous repeat's frames are not kept alive beside the next one's)
+        dt, last = timed(args.steps, prof_mode)
         dts.append(dt)
         if prof_mode and ((it + 1) % PROF_READ == 0 or it == reps - 2):
             p2 = smp.profile_read()
             prof = {k: (prof[k][0] + p2[k][0], prof[k][1] + p2[k][1]) for k in prof}
-    smp.profile_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the walk receives, at its last step: the frames saved for it, the jump x-hat, and the chain state y, v
+        dumped = dump_outputs(args.dump_outputs, {"y_traj_last": last[0][-1], "score_traj_last": last[1][-1], "xhat_traj_last": last[2][-1],
+                                                  "xhat": last[3], "y": y, "v": v})
+    last = None  # (frees the walk's frames before the --full legs)
+    if prof_mode:
+        smp.profile_enable(False)
     prof_all = None
     if prof is not None and rank == 0 and world == 1:
         # per-kernel breakdown from a separate, untimed pass with every class timed
@@ -756,13 +804,11 @@ def main():
         torch.distributed.all_reduce(tot_walkers)
         torch.distributed.all_reduce(tot_atoms)
 
-    rccl = rccl_record(dev, world)
+    rccl = rccl_record(dev, world) if args.full else None
     sharded = None
     grouped = torch.distributed.is_available() and torch.distributed.is_initialized()  # (under a launcher even one rank has a group: the RCCL path runs)
     # (the leg itself runs at the very end, when rank 0's line is complete but for it: `_guarded_sharded_leg`)
-    sharded_wanted = ((world > 1 and not args.no_e2e) or (grouped and args.sharded_leg)) and args.walkers is None and args.atoms is None
-    if sharded_wanted:
-        y_traj = score_traj = xhat_traj = None  # (free the headline walk's frames)
+    sharded_wanted = ((world > 1 and args.full and not args.no_e2e) or (grouped and args.sharded_leg)) and args.walkers is None and args.atoms is None
 
     if rank == 0:
         total_conf = int(tot_walkers.item()) * args.steps
@@ -885,20 +931,21 @@ def main():
             out["config"]["ref_association_tflops_equiv"] = stats["flop_ref_assoc"] * args.steps / dt_med / 1e12
             if stats.get("n_tail_tiles"):
                 out["config"]["tail_tiles"] = f"{stats['n_tail_tiles']} tiles / {stats['n_tail']} destinations through k_tail_form + k_tail_contract (kernel class conv1)"
-        out["rccl"] = rccl
-        if world == 1:
-            del y_traj, score_traj, xhat_traj
-        if not args.no_also and world == 1 and args.config == "cfg2" and args.walkers is None and args.atoms is None and not args.strong and not args.separable:
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if args.full:
+            out["rccl"] = rccl
+        if args.full and not args.no_also and world == 1 and args.config == "cfg2" and args.walkers is None and args.atoms is None and not args.strong and not args.separable:
             out["also"] = also_legs(model, dev, rank)
-        if not args.no_e2e and world == 1 and args.config in ("cfg2", "cfg2r") and args.walkers is None and args.atoms is None and not args.strong:
+        if args.full and not args.no_e2e and world == 1 and args.config in ("cfg2", "cfg2r") and args.walkers is None and args.atoms is None and not args.strong:
             # (the metric's config only: two 20 000-step batches of cfg2 are 35 s of GPU time per leg; other shapes take minutes)
             out["e2e"] = e2e_legs(model, mols, dev)
             ref = [l for l in out["e2e"]["legs"] if l.get("steps_per_batch") == 20000 and not l.get("writer") and "wall_s" in l]
             if ref:
                 out["e2e"]["ratio_to_value_at_20000_steps_without_writer"] = ref[0]["conformations_per_s"] / out["value"]
-        if not args.no_sweep and world == 1 and args.config in ("cfg2", "cfg2r") and args.walkers is None and not args.strong:
+        if args.full and not args.no_sweep and world == 1 and args.config in ("cfg2", "cfg2r") and args.walkers is None and not args.strong:
             out["batch_sweep"] = batch_sweep(model, args.config, args.atoms, dev, rank)
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             out["secondary_rooflines"] = secondary_rooflines(dev)
         if cpu_line is not None:
             out["cpu_baseline"] = cpu_line

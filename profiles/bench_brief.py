@@ -1,6 +1,6 @@
 """One line per bench.py JSON line on stdin: config, conformations/s, ms per step and the per-kernel-class averages (ms per launch).
 
-    python bench.py --config cfg3 --no-cpu-baseline --no-secondary | python profiles/bench_brief.py
+    python bench.py --config cfg3 --full --no-cpu-baseline --no-secondary | python profiles/bench_brief.py
 """
 import json
 import sys

@@ -12,9 +12,9 @@ PY
 for round in 1 2; do
   for c in "$@"; do
     cp scratch/libs/base_head.so jamun_amd/libjamun_hip.so
-    echo -n "head $c "; python3 bench.py --config $c --no-cpu-baseline --no-secondary --no-e2e --no-sweep --no-also 2>/dev/null | python3 profiles/bench_brief.py
+    echo -n "head $c "; python3 bench.py --config $c --full --no-cpu-baseline --no-secondary --no-e2e --no-sweep --no-also 2>/dev/null | python3 profiles/bench_brief.py
     cp /tmp/new.so jamun_amd/libjamun_hip.so
-    echo -n "new  $c "; python3 bench.py --config $c --no-cpu-baseline --no-secondary --no-e2e --no-sweep --no-also 2>/dev/null | python3 profiles/bench_brief.py
+    echo -n "new  $c "; python3 bench.py --config $c --full --no-cpu-baseline --no-secondary --no-e2e --no-sweep --no-also 2>/dev/null | python3 profiles/bench_brief.py
   done
 done
 cp /tmp/new.so jamun_amd/libjamun_hip.so

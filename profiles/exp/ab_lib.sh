@@ -10,7 +10,7 @@ for round in 1 2; do
   for c in "$@"; do
     for which in head other; do
       if [ $which = head ]; then cp "$head" jamun_amd/libjamun_hip.so; else cp "$other" jamun_amd/libjamun_hip.so; fi
-      echo -n "$which "; python3 bench.py --config $c --no-cpu-baseline --no-secondary --no-e2e --no-sweep 2>/dev/null | python3 profiles/bench_brief.py
+      echo -n "$which "; python3 bench.py --config $c --full --no-cpu-baseline --no-secondary --no-e2e --no-sweep 2>/dev/null | python3 profiles/bench_brief.py
     done
   done
 done

@@ -4,9 +4,12 @@
 
 Inputs are generated from fixed seeds with ``jamun_amd.synth``; outputs come from ``oracle/``.
 ``tests/test_oracle.py::test_cached_oracle_fixtures_are_fresh`` re-runs a prefix of each case on the CPU and checks
-the cache bit for bit, so a stale cache cannot go unnoticed.
+the cache bit for bit, so a stale cache cannot go unnoticed.  Both run under PINNED_ENV (``main`` starts itself again under it):
+one thread, MKL's conditional numerical reproducibility and ATen's generic kernels give the same bits on any x86 CPU, where the
+default thread count and instruction-set dispatch would make the cache depend on the machine that wrote it.
 """
 import os
+import subprocess
 import sys
 
 import numpy as np
@@ -29,6 +32,7 @@ MCMC = dict(delta=0.04, friction=1.0, M=1.0, inverse_temperature=1.0, score_fn_c
 # (fp32 vs fp64 oracle stay at 2e-8 .. 7e-8 nm for all 50 frames); 0.2 and 0.5 are chaotic (1.5e-5 / 5.8e-5 nm at step 21,
 # 5e-2 / 2e-1 nm at step 49).
 GAINS = {"strong": 0.5, "stable": 0.05, "mid": 0.1, "g02": 0.2}
+PINNED_ENV = {"OMP_NUM_THREADS": "1", "MKL_NUM_THREADS": "1", "MKL_CBWR": "COMPATIBLE,STRICT", "ATEN_CPU_CAPABILITY": "default"}
 
 
 def molecules(kind):
@@ -196,6 +200,9 @@ CASES = {
 
 
 def main():
+    if any(os.environ.get(k) != v for k, v in PINNED_ENV.items()):  # (read when torch and MKL start: a child process of its own)
+        raise SystemExit(subprocess.call([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=dict(os.environ, **PINNED_ENV)))
+    torch.set_num_threads(1)
     only = set(sys.argv[1:])
     for name, fn in CASES.items():
         if only and name not in only:

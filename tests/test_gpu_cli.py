@@ -156,14 +156,44 @@ def test_sharded_sampler_inside_an_rccl_group(tmp_path):
     assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["ok"], r.stdout[-1000:]
 
 
+def test_bench_plain_line_times_exactly_its_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: ONE JSON line with the headline keys and nothing measured
+    beside it, one timed walk of K steps, and the last step's outputs as float32 .npy files — bit-identical in a second run."""
+    import subprocess
+    import sys
+
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 6 and d["warmup"] == 2 and d["timed_repeats"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 256 * 6 / (d["ms_per_step"] * 6e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "kernel_avg_ms", "also", "e2e", "batch_sweep", "secondary_rooflines", "cpu_baseline", "rccl", "e2e_sharded"):
+        assert k not in d, k
+    names = sorted(f for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(f"{k}.npy" for k in ("y_traj_last", "score_traj_last", "xhat_traj_last", "xhat", "y", "v"))
+    assert d["dumped_outputs"]["arrays"] == {f[:-4]: [256 * 17, 3] for f in names}
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape == (256 * 17, 3) and np.isfinite(a).all(), f
+        assert np.array_equal(a, b), f
+
+
 def test_bench_line_contract_and_roofline_invariants():
-    """`python bench.py` (short run, no CPU baseline): ONE JSON line with the driver's keys; the roofline block prices the dominant kernel's
+    """`python bench.py --full` (short run, no CPU baseline): ONE JSON line with the driver's keys; the roofline block prices the dominant kernel's
     EXECUTED f16 MFMA FLOPs against the dense f16 peak (at most 1 by construction), the useful part is a part of them, and the counted
     bytes stand beside the algorithmic ones."""
     import subprocess
     import sys
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "3", "--no-cpu-baseline", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--repeats", "3", "--no-cpu-baseline", "--no-secondary", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -197,7 +227,7 @@ def test_bench_sharded_leg_on_a_one_rank_rccl_group():
 
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sharded-leg", "--steps", "4", "--warmup", "1", "--repeats", "2", "--no-cpu-baseline",
-                        "--no-secondary", "--no-sweep", "--no-also", "--no-e2e"], env=dict(env, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577"), capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-secondary", "--no-sweep", "--no-also", "--no-e2e", "--full"], env=dict(env, MASTER_ADDR="127.0.0.1", MASTER_PORT="29577"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["rccl"]["backend"].startswith("nccl") and d["rccl"]["world"] == 1 and d["rccl"]["ranks_seen"] == 1

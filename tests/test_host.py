@@ -508,6 +508,7 @@ from jamun_amd import dist, synth
 from jamun_amd.callbacks import SaveTrajectoryCallback
 from jamun_amd.data import WalkerBatch
 from jamun_amd.sampling import Sampler
+dist.local_device = lambda: torch.device("cpu")  # the host path this test is about, also where a GPU is visible (the stubs live on the CPU)
 rank, world = dist.init_process_group("gloo")
 assert world == 2
 # ---- (1) gather with a rank that owns NO walker of a label: rank 1 contributes nothing for label "a"
@@ -599,7 +600,7 @@ def test_bench_self_launches_ranks(tmp_path):
     """`python bench.py --gpus 2` without a launcher spawns the two ranks itself (before any GPU call) and relays ONE JSON
     line from rank 0; --dry-run keeps the rank plumbing (gloo) and skips the kernels."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--dry-run", "--full"],
                        env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -614,10 +615,13 @@ def test_bench_self_launches_ranks(tmp_path):
     assert sh["joined_shape"] == [17, 7 * 2 * 8, 3]  # every walker of both ranks, both batches, in the joined file on rank 0
     assert sh["gather_bytes"] == 2 * 3 * 17 * 8 * 3 * 4  # rank 1's three walkers crossed ranks, once per batch
     assert 0.0 < sh["gather_s"] <= sh["wall_s"] and sh["conformations_per_s"] > 0 and sh["files_written"] >= 2 * 8
-    # under a launcher (WORLD_SIZE set) the script must NOT spawn again: a single rank with WORLD_SIZE=1 just runs
+    # under a launcher (WORLD_SIZE set) the script must NOT spawn again: a single rank with WORLD_SIZE=1 just runs; without --full
+    # the line carries neither the sharded leg nor the rank record
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dry-run"], env=dict(env, WORLD_SIZE="1", RANK="0"),
                         capture_output=True, text=True, timeout=240)
-    assert r1.returncode == 0 and json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])["n_gpus"] == 1
+    assert r1.returncode == 0
+    d1 = json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][-1])
+    assert d1["n_gpus"] == 1 and "e2e_sharded" not in d1 and "rccl" not in d1
 
 
 def test_bench_self_launch_supervises_its_ranks():
@@ -879,3 +883,28 @@ def test_bench_sharded_leg_cannot_cost_the_line_its_headline():
     assert r.returncode == 0 and "not reached" not in r.stdout
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["value"] == 2.5 and "did not return" in line["e2e_sharded"]["error"]
+
+
+def test_bench_dump_outputs_are_float32_and_a_seeded_sample_above_the_cap(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR` writes one float32 .npy per array; above the cap every array keeps the SAME seeded rows, whose indices
+    are written beside them (float64), and a second dump of the same arrays is identical file for file."""
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    arrays = {"y": torch.randn(1000, 3, generator=g), "v": torch.randn(1000, 3, generator=g, dtype=torch.float64)}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert shapes == {"y": [1000, 3], "v": [1000, 3]} and sorted(os.listdir(tmp_path / "all")) == ["v.npy", "y.npy"]
+    for k, t in arrays.items():
+        a = np.load(tmp_path / "all" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays)
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 4096 + 3 * 128  # (+ the .npy headers)
+    for k, t in arrays.items():
+        a = np.load(tmp_path / "a" / f"{k}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy()[rows.astype(np.int64)])
+    for f in os.listdir(tmp_path / "a"):
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f

@@ -229,26 +229,43 @@ def test_separable_tensor_product_counts_and_equivariance():
     assert (f(x, v @ P.T) - out).abs().max() > 1e-3
 
 
-def test_cached_oracle_fixtures_are_fresh(golden_dir):
-    """The GPU tests read cached oracle outputs; re-run a prefix of each kind here and compare bit for bit."""
+def test_cached_oracle_fixtures_are_fresh(golden_dir, tmp_path):
+    """The GPU tests read cached oracle outputs; re-run a prefix of each kind here and compare bit for bit.  The prefix runs in a child
+    process under the generator's PINNED_ENV (one thread, reproducible MKL, generic ATen kernels), the environment the cache was
+    written under, so that the bits do not depend on this machine's CPU or thread count."""
     import importlib.util
+    import json
+    import subprocess
+    import sys
 
-    spec = importlib.util.spec_from_file_location("make_oracle_fixtures", os.path.join(golden_dir, "make_oracle_fixtures.py"))
+    path = os.path.join(golden_dir, "make_oracle_fixtures.py")
+    spec = importlib.util.spec_from_file_location("make_oracle_fixtures", path)
     mk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mk)
-    for name, kw, keys in [
+    cases = [
         ("oracle_forward_ag4", {}, ["xhat", "score", "x3", "deg"]),
         ("oracle_forward_sep_ag4", {}, ["xhat", "x2", "deg"]),
         ("oracle_walk_baoab_ag4_50", {"max_steps": 3}, ["xhat_traj", "y_traj"]),
         ("oracle_walk_baoab_ag4_50_mid", {"max_steps": 3}, ["xhat_traj", "y_traj"]),
         ("oracle_walk_aboba_ag4_20", {"max_steps": 3}, ["xhat_traj", "y_traj"]),
         ("oracle_sampler_cc0", {"max_batches": 1}, ["xhat_traj_0"]),
-    ]:
-        fresh = mk.CASES[name](**kw)
+    ]
+    code = ("import importlib.util, json, sys\nimport numpy as np, torch\ntorch.set_num_threads(1)\n"
+            "spec = importlib.util.spec_from_file_location('mk', sys.argv[1]); mk = importlib.util.module_from_spec(spec); spec.loader.exec_module(mk)\n"
+            "out = {}\n"
+            "for name, kw, keys in json.loads(sys.argv[3]):\n"
+            "    f = mk.CASES[name](**kw)\n"
+            "    out.update({name + '__' + k: f[k].numpy() for k in keys})\n"
+            "np.savez(sys.argv[2], **out)\n")
+    r = subprocess.run([sys.executable, "-c", code, path, str(tmp_path / "fresh.npz"), json.dumps(cases)], env=dict(os.environ, **mk.PINNED_ENV),
+                       capture_output=True, text=True, timeout=1200)
+    assert r.returncode == 0, r.stderr[-3000:]
+    fresh = np.load(tmp_path / "fresh.npz")
+    for name, kw, keys in cases:
         cached = np.load(os.path.join(golden_dir, name + ".npz"))
         for k in keys:
             c = torch.tensor(cached[k])
-            f = fresh[k]
+            f = torch.tensor(fresh[name + "__" + k])
             assert torch.equal(f, c[: f.shape[0]] if f.shape != c.shape else c), (name, k)
 
 
