@@ -328,6 +328,25 @@ int jamun_debug_stamps(unsigned long long* out8);
  *   what = 2: network output g [n_atoms,3] (before c_skip/c_out)                          */
 int jamun_debug_read(jamun_sampler* s, int32_t what, int32_t layer, float* out_dev, void* stream);
 
+/* Work lists of the destination-grouped conv kernels (tests/test_plan.py, tests/test_gpu_plans.py).  Segment records are int4 pairs
+ * {tile, partial slab, k_begin, k_end}, {k_extra (-1: none), ...}, [grid][max_segs][2]; padding records have tile = -1.
+ *
+ * Host only, no device calls: runs the planner of jamun_sampler_create on caller-given tiles — tile_atoms [n_tiles][2] {first atom, atoms},
+ * tile_chunk [n_tiles] (destination chunk; tiles of one chunk number their slabs jointly), tile_weight [n_tiles] (>= 1), skip [n_tiles]
+ * (NULL: none; non-zero: the tile is not on this plan) — with cus workgroups, ng hidden-unit slices (1, 2, 4, 8; cus % 8 == 0 above 1),
+ * n_k >= ng hidden units and seg_cost (a segment's prologue + epilogue in items, 0..1000).  Writes max_segs, n_slabs, atom_nslab [n_atoms]
+ * and, when segs_out is not NULL, the records (segs_capacity >= cus * max_segs * 8 int32 values, else JAMUN_ERR_INVALID with max_segs written). */
+int jamun_debug_plan_segments(int32_t cus, int32_t ng, int32_t n_k, int32_t n_atoms, int32_t n_tiles, const int32_t* tile_atoms,
+                              const int32_t* tile_chunk, int32_t n_chunks, const int64_t* tile_weight, const int8_t* skip, double seg_cost,
+                              int32_t* segs_out, int64_t segs_capacity, int32_t* max_segs, int32_t* n_slabs, int32_t* atom_nslab);
+/* The lists a sampler's kernels run, copied to the host (synchronous; the sampler needs a destination-grouped plan):
+ *   which = 0: hidden layers' segment records (the second record carries the tile descriptor {k_extra, first atom, atoms | rows << 8, first row})
+ *           1: the initial projector's own records (none when it runs list 0)     2: tail-tile records [n_tail_tiles] int4
+ *           3: tile table [n_tiles] {first atom, atoms, first source row, end}    4 / 5: partial slabs per atom [n_atoms] of list 0 / 1
+ * info[9] = {int32 values of the list, grid, max_segs, n_slabs, k-slices, n_k, n_tiles, segment cost in tenths, tail runs}; out may be NULL
+ * (info only), else capacity >= info[0]. */
+int jamun_debug_segments(jamun_sampler* s, int32_t which, int32_t* out, int64_t capacity, int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

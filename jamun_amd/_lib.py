@@ -130,6 +130,9 @@ SYMBOLS = {
     "jamun_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), _P]),
     "jamun_debug_stamps": (C.c_int, [C.POINTER(C.c_uint64)]),
     "jamun_debug_read": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
+    "jamun_debug_plan_segments": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_double,
+                                            _P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "jamun_debug_segments": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
 }
 
 PROF_CLASSES = ["geom", "edge_h", "conv0_init", "conv1_init", "conv0", "conv1", "node_update", "head_finalize", "tprod"]

@@ -336,6 +336,7 @@ struct jamun_sampler {
   int dg_mode = 0;  // 0 two-phase resident, 1 alternating residency, 2 single phase (see jamun_sampler_create)
   int dg_emu = 1;   // 1: f16x3 contraction (three f16 MFMAs per fp32 product); 0 (jamun_tuning.dg_fp32): v_mfma_f32_32x32x2_f32; stats report 2 for the opt-in f16x1 mode (s->x1)
   int dg_RS = 0, dg_grid = 0, dg_max_segs = 0, dg_n_slabs = 0, dg_n_tiles = 0;
+  int dg_ng = 1, dg_seg_cost_tenths = 0;  // k-slices and segment cost the work lists were cut with (jamun_debug_segments)
   int2 *dg_tile_atoms = nullptr, *dg_tile_span = nullptr;
   int4* dg_segs = nullptr;
   int* dg_atom_nslab = nullptr;
@@ -1652,9 +1653,10 @@ SegPlan plan_segments(int cus, int ng, int n_k, int N, const std::vector<int2>& 
         const double w = (double)weight_of(t) * unit;
         int i0 = 0;
         while (i0 < cnt) {
-          int take = (int)std::floor((budget - acc - seg_cost) / w + 1e-9);
-          if (take < 1 && acc > 0) { ++c; acc = 0; continue; }  // (no room for a segment with one item: next workgroup)
-          take = std::max(1, std::min(take, cnt - i0));
+          // (the room in double: a wide budget over a light tile's weight exceeds the int range)
+          const double room = std::floor((budget - acc - seg_cost) / w + 1e-9);
+          if (room < 1 && acc > 0) { ++c; acc = 0; continue; }  // (no room for a segment with one item: next workgroup)
+          const int take = room < 1 ? 1 : (int)std::min<double>(room, cnt - i0);
           if (c >= ncx) return false;
           if (out) {
             const int i1 = i0 + take;
@@ -2139,6 +2141,8 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
           }
         }
         s->dg_grid = cus;
+        s->dg_ng = ng;
+        s->dg_seg_cost_tenths = (int)std::lround(10 * seg_cost);
         s->dg_max_segs = P.max_segs;
         embed(P.segs);
         s->dg_segs = dev_upload(P.segs);
@@ -2752,6 +2756,77 @@ int jamun_debug_read(jamun_sampler* s, int32_t what, int32_t layer, float* out, 
       throw Err(JAMUN_ERR_INVALID, "unknown debug buffer");
     }
     HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_debug_plan_segments(int32_t cus, int32_t ng, int32_t n_k, int32_t n_atoms, int32_t n_tiles, const int32_t* tile_atoms,
+                              const int32_t* tile_chunk, int32_t n_chunks, const int64_t* tile_weight, const int8_t* skip, double seg_cost,
+                              int32_t* segs_out, int64_t segs_capacity, int32_t* max_segs, int32_t* n_slabs, int32_t* atom_nslab) {
+  return guarded([&] {
+    if (!max_segs || !n_slabs || !atom_nslab || (n_tiles > 0 && (!tile_atoms || !tile_chunk || !tile_weight)))
+      throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (cus < 1 || n_atoms < 0 || n_tiles < 0 || n_chunks < 0) throw Err(JAMUN_ERR_INVALID, "bad sizes");
+    if ((ng != 1 && ng != 2 && ng != 4 && ng != 8) || (ng > 1 && cus % 8 != 0) || n_k < ng)
+      throw Err(JAMUN_ERR_INVALID, "ng must be 1, 2, 4 or 8, with cus % 8 == 0 and n_k >= ng when above 1 (as jamun_sampler_create)");
+    if (!(seg_cost >= 0.0 && seg_cost <= 1000.0)) throw Err(JAMUN_ERR_INVALID, "seg_cost out of range [0, 1000]");
+    std::vector<int2> t_atoms((size_t)n_tiles);
+    std::vector<int> t_chunk((size_t)n_tiles);
+    std::vector<int64_t> w((size_t)n_tiles);
+    std::vector<char> sk((size_t)n_tiles, 0);
+    for (int t = 0; t < n_tiles; ++t) {
+      t_atoms[t] = make_int2(tile_atoms[2 * t], tile_atoms[2 * t + 1]);
+      if (t_atoms[t].x < 0 || t_atoms[t].y < 1 || t_atoms[t].y > 32 || t_atoms[t].x + t_atoms[t].y > n_atoms) throw Err(JAMUN_ERR_INVALID, "tile atoms out of range");
+      t_chunk[t] = tile_chunk[t];
+      if (t_chunk[t] < 0 || t_chunk[t] >= n_chunks) throw Err(JAMUN_ERR_INVALID, "tile chunk out of range");
+      w[t] = tile_weight[t];
+      if (w[t] < 1) throw Err(JAMUN_ERR_INVALID, "tile weights must be >= 1");
+      sk[t] = skip ? (char)(skip[t] != 0) : 0;
+    }
+    // (the sampler's own planner: the same function, only the tile weights come from the caller)
+    SegPlan P = plan_segments(cus, ng, n_k, n_atoms, t_atoms, t_chunk, n_chunks, [&](int t) -> int64_t { return w[t]; }, skip ? &sk : nullptr, seg_cost);
+    *max_segs = P.max_segs;
+    *n_slabs = P.n_slabs;
+    std::copy(P.atom_nslab.begin(), P.atom_nslab.end(), atom_nslab);
+    if (segs_out) {
+      if ((int64_t)P.segs.size() * 4 > segs_capacity) throw Err(JAMUN_ERR_INVALID, "segs_out too small: needs cus * max_segs * 8 values");
+      std::memcpy(segs_out, P.segs.data(), P.segs.size() * sizeof(int4));
+    }
+  });
+}
+
+int jamun_debug_segments(jamun_sampler* s, int32_t which, int32_t* out, int64_t capacity, int32_t* info) {
+  return guarded([&] {
+    if (!s || !info) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (!s->dg_on) throw Err(JAMUN_ERR_INVALID, "the sampler has no destination-grouped plan (jamun_tuning.no_dg)");
+    const void* src = nullptr;
+    int64_t n = 0;
+    int max_segs = s->dg_max_segs, n_slabs = s->dg_n_slabs;
+    switch (which) {
+      case 0: src = s->dg_segs; n = (int64_t)s->dg_grid * s->dg_max_segs * 8; break;
+      case 1:
+        max_segs = s->init_max_segs; n_slabs = s->init_n_slabs;
+        if (s->init_segs) { src = s->init_segs; n = (int64_t)s->dg_grid * s->init_max_segs * 8; }
+        break;
+      case 2: src = s->tail_tiles; n = (int64_t)s->n_tail_tiles * 4; break;
+      case 3: n = (int64_t)s->dg_n_tiles * 4; break;
+      case 4: src = s->dg_atom_nslab; n = s->n_atoms; break;
+      case 5: if (s->init_atom_nslab) { src = s->init_atom_nslab; n = s->n_atoms; } break;
+      default: throw Err(JAMUN_ERR_INVALID, "unknown work list");
+    }
+    const int32_t v[9] = {(int32_t)n, s->dg_grid, max_segs, n_slabs, s->dg_ng, s->hp.edge_attr_dim + 1, s->dg_n_tiles, s->dg_seg_cost_tenths, s->tail_runs};
+    std::copy(v, v + 9, info);
+    if (!out || n == 0) return;
+    if (n > capacity) throw Err(JAMUN_ERR_INVALID, "out too small: needs info[0] values");
+    if (which == 3) {  // {first atom, atoms, first source row, end of the source rows} per tile
+      std::vector<int2> a((size_t)s->dg_n_tiles), sp((size_t)s->dg_n_tiles);
+      HIPCHECK(hipMemcpy(a.data(), s->dg_tile_atoms, a.size() * sizeof(int2), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(sp.data(), s->dg_tile_span, sp.size() * sizeof(int2), hipMemcpyDeviceToHost));
+      for (size_t t = 0; t < a.size(); ++t) {
+        out[4 * t] = a[t].x; out[4 * t + 1] = a[t].y; out[4 * t + 2] = sp[t].x; out[4 * t + 3] = sp[t].y;
+      }
+      return;
+    }
+    HIPCHECK(hipMemcpy(out, src, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
   });
 }
 

@@ -283,6 +283,54 @@ class NativeSampler:
             _lib.check(self._lib.jamun_debug_read(self._h, what, layer, _ptr(out), _stream()))
         return out
 
+    def debug_segments(self, which: int) -> tuple:
+        """``jamun_debug_segments``: a work list the destination-grouped kernels run, copied to the host — (int32 numpy array, info dict).
+        which 0 / 1: segment records [grid, max_segs, 2, 4] of the hidden layers / the initial projector (empty: it runs list 0); 2: tail-tile
+        records [n_tail_tiles, 4]; 3: tile table [n_tiles, 4]; 4 / 5: partial slabs per atom of list 0 / 1."""
+        import numpy as np
+
+        info = (C.c_int32 * 9)()
+        _lib.check(self._lib.jamun_debug_segments(self._h, int(which), None, 0, info))
+        n = int(info[0])
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.jamun_debug_segments(self._h, int(which), out.ctypes.data_as(C.c_void_p), out.size, info))
+        keys = ("n_values", "grid", "max_segs", "n_slabs", "ng", "n_k", "n_tiles", "seg_cost_tenths", "tail_runs")
+        meta = {k: int(info[i]) for i, k in enumerate(keys)}
+        out = out[:n]
+        if which in (0, 1):
+            out = out.reshape(meta["grid"], meta["max_segs"], 2, 4) if n else out.reshape(0, 0, 2, 4)
+        elif which in (2, 3):
+            out = out.reshape(-1, 4)
+        return out, meta
+
+
+def plan_segments(cus: int, ng: int, n_k: int, n_atoms: int, tile_atoms, tile_chunk, tile_weight, skip=None, seg_cost: float = 0.0) -> dict:
+    """``jamun_debug_plan_segments``: the work-list planner of jamun_sampler_create, run on the host on the given tiles (no GPU needed).
+    tile_atoms [n_tiles, 2] {first atom, atoms}; tile_chunk [n_tiles]; tile_weight [n_tiles] (>= 1); skip [n_tiles] or None.
+    Returns {"segs": int32 [cus, max_segs, 2, 4], "max_segs", "n_slabs", "atom_nslab": int32 [n_atoms]}."""
+    import numpy as np
+
+    lib = _lib.load()
+    ta = np.ascontiguousarray(tile_atoms, dtype=np.int32).reshape(-1, 2)
+    n_tiles = ta.shape[0]
+    tc = np.ascontiguousarray(tile_chunk, dtype=np.int32).reshape(n_tiles)
+    tw = np.ascontiguousarray(tile_weight, dtype=np.int64).reshape(n_tiles)
+    sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.int8).reshape(n_tiles)
+    n_chunks = int(tc.max()) + 1 if n_tiles else 0
+    ms, nsl = C.c_int32(), C.c_int32()
+    nslab = np.zeros(max(n_atoms, 1), dtype=np.int32)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    args = (int(cus), int(ng), int(n_k), int(n_atoms), n_tiles, vp(ta), vp(tc), n_chunks, vp(tw), vp(sk), float(seg_cost))
+    segs = np.zeros((int(cus), 16, 2, 4), dtype=np.int32)
+    code = lib.jamun_debug_plan_segments(*args, vp(segs), segs.size, C.byref(ms), C.byref(nsl), vp(nslab))
+    if code != 0 and ms.value > segs.shape[1]:  # (longer lists than the first guess: max_segs is written, plan into a buffer of that size)
+        segs = np.zeros((int(cus), ms.value, 2, 4), dtype=np.int32)
+        code = lib.jamun_debug_plan_segments(*args, vp(segs), segs.size, C.byref(ms), C.byref(nsl), vp(nslab))
+    _lib.check(code)
+    segs = segs.reshape(-1)[: int(cus) * ms.value * 8].reshape(int(cus), ms.value, 2, 4).copy()
+    return {"segs": segs, "max_segs": ms.value, "n_slabs": nsl.value, "atom_nslab": nslab[:n_atoms].copy()}
+
 
 # ---- stand-alone operators --------------------------------------------------------------------------------------
 
