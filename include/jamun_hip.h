@@ -250,12 +250,14 @@ typedef struct jamun_stats {
   int64_t n_edges;        /* directed edges (radial + bonded) in the last forward             */
   int64_t flop_ref_assoc; /* FLOPs of one forward in the reference association (SURVEY §8 d)  */
   int64_t flop_executed;  /* FLOPs actually issued on MFMA/VALU by this implementation         */
-  int64_t conv_k0, conv_k1; /* padded contraction depth of the scalar / vector conv GEMMs (hidden layer) */
-  int64_t conv0_flop_alg;   /* useful FLOPs of ONE hidden-layer scalar-row conv launch: 2*n_atoms*65*(mul0+mul1)*(mul0+mul1) */
-  int64_t conv1_flop_alg;   /* useful FLOPs of ONE hidden-layer vector-row conv launch: 2*3*n_atoms*65*(mul0+2*mul1)*mul1   */
+  int64_t conv_k0, conv_k1; /* padded contraction depth of the scalar / vector conv GEMMs (hidden layer; H + 1 hidden rows, H = edge_attr_dim) */
+  int64_t conv0_flop_alg;   /* useful FLOPs of ONE hidden-layer scalar-row conv launch: 2*n_atoms*(H+1)*(mul0+mul1)*(mul0+mul1) (H + 1 = 65 by default) */
+  int64_t conv1_flop_alg;   /* useful FLOPs of ONE hidden-layer vector-row conv launch: 2*3*n_atoms*(H+1)*(mul0+2*mul1)*mul1   */
   int32_t edge_stride;
   int32_t n_slices;       /* partial slabs per tile summed by the node update (max over tiles)          */
-  int32_t conv_path;      /* hidden layers: 2 destination-grouped kernels on host-planned tiles (jamun_conv_mf.hip / jamun_conv_dg.hip),
+  int32_t conv_path;      /* hidden layers: 3 the wide path (jamun_wide.hip: Conv models outside the compiled-width kernels' envelope — any
+                             hidden width, edge_attr_dim != 64, embeddings above 224 channels; fp32 MFMAs, jamun_tuning.f16x1 ignored),
+                             2 destination-grouped kernels on host-planned tiles (jamun_conv_mf.hip / jamun_conv_dg.hip),
                              0 general k_conv (any irreps, any topology; also SeparableConv's slot in this field) */
   int32_t dg_mode;        /* destination-grouped kernel: 5 jamun_conv_ml.hip (as 4, for source spans of 63..167 atoms: two passes over the hidden
                              units with the vector / scalar channels resident, block-sparse forming over the occupied 16-row source blocks);
@@ -264,7 +266,7 @@ typedef struct jamun_stats {
                              0 two phases per hidden unit with resident source rows, 1 two passes over the hidden units (molecules above
                              ~80 atoms), 2 single phase (spans up to ~52 atoms), 3 single phase with one Y tile (spans up to ~73 atoms);
                              -1: not in use */
-  int32_t init_path;      /* initial projector: 5 k_conv_mlx (jamun_conv_ml.hip: as 4 on the dg_mode 5 tiles — source spans of 63..167 atoms, block-sparse forming),
+  int32_t init_path;      /* initial projector: 6 k_conv_wide (the wide path, conv_path 3), 5 k_conv_mlx (jamun_conv_ml.hip: as 4 on the dg_mode 5 tiles — source spans of 63..167 atoms, block-sparse forming),
                              4 k_conv_mfx (jamun_conv_mf.hip: aggregated operand formed on the matrix cores from the embedding
                              rows, as a hidden layer with 64 scalar channels; dg_mode 4 tiles, any number of distinct embedding rows),
                              3 k_conv_mfi (coefficient sums per distinct embedding row formed with a one-hot selector, contracted with the
@@ -273,7 +275,7 @@ typedef struct jamun_stats {
                              0 the general kernel k_conv  (1 was the table kernel jamun_conv_init.hip, retired in round 4) */
   int32_t dg_row_blocks;  /* jamun_conv_dg.hip: 1 when some molecule exceeds the span budget and its sources are cut into row blocks */
   int32_t dg_emu;         /* hidden-layer conv arithmetic: 2 f16x1 (jamun_tuning.f16x1: one f16 MFMA per product; k_conv_mf / k_conv_ml only), 1 f16x3 (three v_mfma_f32_*_f16 per fp32 product, operands split hi + lo),
-                             0 v_mfma_f32_32x32x2_f32 (jamun_tuning.dg_fp32); -1: not in use */
+                             0 v_mfma_f32_32x32x2_f32 (jamun_tuning.dg_fp32; always on the wide path, conv_path 3); -1: not in use */
   int64_t conv_flop_exec_launch; /* matrix-core FLOPs EXECUTED by ONE launch of the hidden-layer conv kernel (k_conv_mf / k_conv_dg; padding,
                              structural zeros of the forming GEMMs and the three products of the f16x3 scheme included; the T pre-pass is
                              a separate launch and not counted); 0 when another conv path is in use */

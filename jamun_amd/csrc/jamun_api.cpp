@@ -134,6 +134,8 @@ struct LayerDev {
   int K0h = 0, K1h = 0;
   float *kga0 = nullptr, *kga1 = nullptr, *kgx = nullptr, *cg0 = nullptr, *cg1 = nullptr;  // its row (input) / column (output) powers of two
   float* mix = nullptr;
+  float4 *wn0 = nullptr, *wn1 = nullptr;  // wide path (k_node_lin_wide): [W_self ; W_skip] with the K order of NodeWideArgs
+  int K0w = 0, K1w = 0;
   int in0 = 0, in1 = 0, XSin = 0;
   int64_t tp_numel = 0;
 };
@@ -237,14 +239,38 @@ std::vector<std::pair<int, int>> k_subgroups(int n_k, int n_slices, int ksub, st
   return subs;
 }
 
+// The wide kernel (k_conv_wide) forms k-subgroups of any size 1..ksub: a slice of `size` hidden units is cut into
+// ceil(size / ksub) near-equal subgroups; slices may be empty (n_k < n_slices).
+std::vector<std::pair<int, int>> k_subgroups_any(int n_k, int n_slices, int ksub, std::vector<int>& slice_first_sub) {
+  std::vector<std::pair<int, int>> subs;
+  slice_first_sub.assign(n_slices + 1, 0);
+  const int base = n_k / n_slices, rem = n_k % n_slices;
+  int k = 0;
+  for (int s = 0; s < n_slices; ++s) {
+    const int size = base + (s >= n_slices - rem ? 1 : 0);
+    slice_first_sub[s] = (int)subs.size();
+    if (size == 0) continue;
+    const int n_sub = (size + ksub - 1) / ksub;
+    const int lo = size / n_sub, n_hi = size % n_sub;
+    for (int i = 0; i < n_sub; ++i) {
+      const int ks = lo + (i < n_hi ? 1 : 0);
+      subs.push_back({k, ks});
+      k += ks;
+    }
+  }
+  slice_first_sub[n_slices] = (int)subs.size();
+  return subs;
+}
+
+// (wide = true: the chunking of k_conv_wide — k-subgroups of 1..ksub, an even number of weight groups per chunk)
 ConvProblemDev pack_problem(const std::vector<UBlock>& blocks, int planes, int G, int n_slices, int ksub,
-                            const std::vector<float>& W3, const std::vector<float>& b3, int hidden) {
+                            const std::vector<float>& W3, const std::vector<float>& b3, int hidden, bool wide = false) {
   ConvProblemDev P;
   P.planes = planes;
   P.nt = (G + 31) / 32;
   const int NT = P.nt;
   std::vector<int> first_sub;
-  const auto subs = k_subgroups(hidden + 1, n_slices, ksub, first_sub);
+  const auto subs = wide ? k_subgroups_any(hidden + 1, n_slices, ksub, first_sub) : k_subgroups(hidden + 1, n_slices, ksub, first_sub);
   std::vector<int4> chunks;
   std::vector<int> sp(n_slices + 1, 0);
   int64_t gofs = 0;  // in weight groups (4 K-steps x NT tiles x 64 lanes x float)
@@ -253,7 +279,8 @@ ConvProblemDev pack_problem(const std::vector<UBlock>& blocks, int planes, int G
     for (int si = first_sub[s]; si < first_sub[s + 1]; ++si)  // k-subgroup major: the staged h~ records are reused by the u-blocks
       for (size_t b = 0; b < blocks.size(); ++b) {
         const int nu = (int)blocks[b].e.size(), k0 = subs[si].first, ks = subs[si].second;
-        const int ng = (ks * nu / 2 + 3) / 4;
+        int ng = (ks * nu / 2 + 3) / 4;
+        if (wide) ng = (ng + 1) & ~1;  // (k_conv_wide consumes weight groups in pairs: zero weights and zeroed A rows pad a chunk)
         chunks.push_back(make_int4((int)b, k0 | (ks << 16), (int)gofs, ng));
         gofs += ng;
       }
@@ -367,6 +394,8 @@ struct jamun_sampler {
   int* mf_err = nullptr;  // device flag of k_conv_mf
   int* mf_err_host = nullptr;  // pinned copy, refreshed behind every entry point that ran a forward (mf_err_fetch / mf_err_check)
   float *x_emb = nullptr, *mu = nullptr;
+  bool wide = false;  // the wide path (jamun_wide.hip): a Conv model outside the envelope of the compiled-width kernels
+  float *z0 = nullptr, *z1 = nullptr;  // its node-update operands (NodeWideArgs::z0 / z1)
   std::vector<LayerDev> layers;
   float *w_gate = nullptr, *w_vec = nullptr, *w_out = nullptr;
   // work buffers
@@ -401,8 +430,9 @@ struct jamun_sampler {
       free_problem(L.p0); free_problem(L.p1); free_dg(L.dg);
       hipFree(L.sep.w2b); hipFree(L.sep.cfw); hipFree(L.sep.bias); hipFree(L.sep.wl0); hipFree(L.sep.wl1);
       hipFree(L.wcat0); hipFree(L.wcat1); hipFree(L.wh0); hipFree(L.wh1); hipFree(L.kga0); hipFree(L.kga1); hipFree(L.kgx); hipFree(L.cg0); hipFree(L.cg1); hipFree(L.mix); hipFree(L.tt2); hipFree(L.tabw);
-      hipFree(L.wx); hipFree(L.xph); hipFree(L.xpl); hipFree(L.xcf0); hipFree(L.xcf1);
+      hipFree(L.wx); hipFree(L.xph); hipFree(L.xpl); hipFree(L.xcf0); hipFree(L.xcf1); hipFree(L.wn0); hipFree(L.wn1);
     }
+    hipFree(z0); hipFree(z1);
     hipFree(w_gate); hipFree(w_vec); hipFree(w_out);
     hipFree(yc); hipFree(h); hipFree(partial0); hipFree(partial1); hipFree(g); hipFree(tmp);
     hipFree(xhat_buf); hipFree(score_buf); hipFree(psi); hipFree(deg); hipFree(esrc); hipFree(egeo);
@@ -415,7 +445,7 @@ struct jamun_sampler {
 namespace {
 
 void build_layer_common(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks, const std::vector<double>& s_in,
-                        LayerDev& L, int in0, int in1) {
+                        LayerDev& L, int in0, int in1, bool wide = false) {
   const jamun_hparams& hp = m.hp;
   const int mul0 = hp.mul0, mul1 = hp.mul1, H = hp.edge_attr_dim;
   // ---- radial MLP first layer: split into the constant bonded part and the radial part
@@ -493,6 +523,30 @@ void build_layer_common(const jamun_model& m, const std::string& prefix, const s
         }
     return out;
   };
+  if (wide) {  // k_node_lin_wide: lane (c, hh), element st <-> row 8 g + 4 hh + st (one float4 of a Z row per lane and 4 K-steps)
+    auto pack_wide = [](const std::vector<float>& wself, int ks, const std::vector<float>& wskip, int kk, int ncol, int& Kp) {
+      Kp = (ks + kk + 7) & ~7;
+      const int nt = (ncol + 31) / 32, ng = Kp / 8;
+      std::vector<float4> out((size_t)nt * ng * 64, make_float4(0.f, 0.f, 0.f, 0.f));
+      for (int t = 0; t < nt; ++t)
+        for (int g = 0; g < ng; ++g)
+          for (int lane = 0; lane < 64; ++lane) {
+            const int hh = lane >> 5, c = t * 32 + (lane & 31);
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            for (int st = 0; st < 4; ++st) {
+              const int row = 8 * g + 4 * hh + st;
+              if (c >= ncol) continue;
+              if (row < ks) v[st] = wself[(size_t)row * ncol + c];
+              else if (row < ks + kk) v[st] = wskip[(size_t)(row - ks) * ncol + c];
+            }
+            out[((size_t)t * ng + g) * 64 + lane] = make_float4(v[0], v[1], v[2], v[3]);
+          }
+      return out;
+    };
+    L.wn0 = dev_upload(pack_wide(wf0, mul0, ws0, in0, mul0, L.K0w));
+    L.wn1 = dev_upload(pack_wide(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1w));
+    return;  // (the compiled-width node-update kernels are not used on the wide path)
+  }
   L.wcat0 = dev_upload(pack_cat(wf0, mul0, ws0, in0, mul0, L.K0p));
   L.wcat1 = dev_upload(pack_cat(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1p));
   // f16x3 node update: the same matrices balanced by exact powers of two — row K (an input channel) times 2^-e_K so that its largest
@@ -694,7 +748,7 @@ LayerDev build_layer_separable(const jamun_model& m, const std::string& prefix, 
 LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
                      const std::vector<double>& s_in, int n_slices,
                      const std::vector<float>* uniq_rows = nullptr, int row_len = 0, bool pack_dg = false,
-                     const std::vector<float>* all_rows = nullptr) {
+                     const std::vector<float>* all_rows = nullptr, bool wide = false) {
   const jamun_hparams& hp = m.hp;
   const int mul0 = hp.mul0, mul1 = hp.mul1, G0 = mul0 + mul1, G1 = mul1, H = hp.edge_attr_dim;
   LayerDev L;
@@ -762,6 +816,12 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
     b.e.insert(b.e.end(), crosse.begin() + i, crosse.begin() + hi);
     pad_even(b);
     blocks1.push_back(b);
+  }
+  if (wide) {  // the wide path (jamun_wide.hip): k_conv_wide's chunking, no specialised kernels
+    L.p0 = pack_problem(blocks0, 1, G0, n_slices, JAMUN_WIDE_KSUB0, W3, b3, H, true);
+    L.p1 = pack_problem(blocks1, 3, G1, n_slices, JAMUN_WIDE_KSUB1, W3, b3, H, true);
+    build_layer_common(m, prefix, in_blocks, s_in, L, in0, in1, true);
+    return L;
   }
   L.p0 = pack_problem(blocks0, 1, G0, n_slices, JAMUN_KSUB0, W3, b3, H);
   L.p1 = pack_problem(blocks1, 3, G1, n_slices, JAMUN_KSUB1, W3, b3, H);
@@ -1263,13 +1323,27 @@ struct ProfScope {
 // Geometry of one forward: centring, radius graph + bonded edges, unit vectors and distances (k_geom; `pre`: the first half of a
 // BAOAB iteration fused in front of it), and — when the buffer holds all layers — the radial MLPs' hidden activations of every
 // layer (k_edge_h; they depend on the geometry only).
+// Radial MLPs of the wide path from block layer0 on (h_all: that block's table)
+EdgeHWideArgs edge_h_wide_args(jamun_sampler* s, int layer0) {
+  EdgeHWideArgs e{};
+  e.deg = s->deg; e.esrc = s->esrc; e.egeo = s->egeo; e.n_atoms = s->n_atoms; e.S = s->S;
+  e.H = s->hp.edge_attr_dim; e.nr = (s->hp.edge_attr_dim + 1) / 2; e.layer0 = layer0;
+  e.w1r_all = s->w1r_all; e.cmask_all = s->cmask_all; e.mu = s->mu; e.step = s->rb_step;
+  e.h_all = s->h + (s->h_batched ? (size_t)layer0 * s->h_stride : 0);
+  e.h_layer_stride = s->h_stride; e.h_kstride = s->h_kstride;
+  return e;
+}
+
 void build_edges(jamun_sampler* s, float* y, hipStream_t st, const LangevinPre& pre = LangevinPre(), bool geom_done = false) {
   if (!geom_done) {  // (geom_done: the previous walk iteration's last launch, k_finalize_geom, already advanced y and built the edge table)
     ProfScope ps(s, JAMUN_PROF_GEOM, st);
     launch_geom(y, s->ptr, s->n_graphs, s->c_in, s->r2, s->S, s->bond_in_ptr, s->bond_in_src, s->hp.mean_center, s->yc,
                 s->deg, s->esrc, s->egeo, s->epair, pre, st);
   }
-  if (s->h_batched) {
+  if (s->h_batched && s->wide) {
+    ProfScope ps(s, JAMUN_PROF_EDGE_H, st);
+    launch_edge_h_wide(edge_h_wide_args(s, 0), (int)s->layers.size(), st);
+  } else if (s->h_batched) {
     ProfScope ps(s, JAMUN_PROF_EDGE_H, st);
     launch_edge_h(s->deg, s->esrc, s->egeo, s->n_atoms, s->S, s->w1r_all, s->cmask_all, (int)s->layers.size(), s->mu, s->rb_step, s->h,
                   s->h_stride, s->h_kstride, st, s->w1h_all, s->w1isc_all);
@@ -1279,7 +1353,45 @@ void build_edges(jamun_sampler* s, float* y, hipStream_t st, const LangevinPre& 
 
 // One block of the network on the current edge table: ConvBlock l (conv contraction + gate + self-interaction + skip Linear)
 // and, for the hidden layers, the noise-conditional input scaling and skip mix around it (e3conv.py:129-133).
+// The same block on the wide path (jamun_wide.hip): k_edge_h_wide (when not batched), k_conv_wide for the scalar and the
+// vector rows, k_node_gate_wide + k_node_lin_wide.
+void run_layer_wide(jamun_sampler* s, size_t l, const float* x_in, int XSin, float* x_out, hipStream_t st) {
+  LayerDev& L = s->layers[l];
+  const float* h_l = s->h + (s->h_batched ? l * s->h_stride : 0);
+  if (!s->h_batched) {
+    ProfScope ps(s, JAMUN_PROF_EDGE_H, st);
+    launch_edge_h_wide(edge_h_wide_args(s, (int)l), 1, st);
+  }
+  ConvArgs a{};
+  a.deg = s->deg; a.esrc = s->esrc; a.egeo = s->egeo; a.h = h_l; a.h_kstride = s->h_kstride; a.x = x_in;
+  a.n_atoms = s->n_atoms; a.n_pad = s->n_pad; a.n_tiles = s->n_tiles; a.S = s->S; a.S4 = (s->S + 3) & ~3; a.XS = XSin;
+  a.n_slices = s->n_slices;
+  for (int pi = 0; pi < 2; ++pi) {
+    ConvProblemDev& P = pi == 0 ? L.p0 : L.p1;
+    if (P.nt == 0) continue;
+    a.wpack = P.wpack; a.chunks = P.chunks; a.slice_ptr = P.slice_ptr; a.ublk = P.ublk; a.lane_xoff = P.lane_xoff;
+    a.partial = pi == 0 ? s->partial0 : s->partial1;
+    ProfScope ps(s, l == 0 ? (pi == 0 ? JAMUN_PROF_CONV0_INIT : JAMUN_PROF_CONV1_INIT) : (pi == 0 ? JAMUN_PROF_CONV0 : JAMUN_PROF_CONV1), st);
+    const int rcode = launch_conv_wide(a, P.planes, P.nt, st);
+    if (rcode == -2) throw Err(JAMUN_ERR_INVALID, "walker batch needs more than 160 KiB of LDS per wide conv workgroup (edge stride too large)");
+    if (rcode != 0) throw Err(JAMUN_ERR_INVALID, "unsupported wide conv tile configuration");
+  }
+  NodeWideArgs n{};
+  n.partial0 = s->partial0; n.partial1 = s->partial1; n.deg = s->deg; n.x_in = x_in; n.x_out = x_out; n.z0 = s->z0; n.z1 = s->z1;
+  n.wn0 = L.wn0; n.wn1 = L.wn1; n.K0p = L.K0w; n.K1p = L.K1w; n.mix = L.mix;
+  n.cL = s->hp.act_scalar_const; n.cS = s->hp.act_gate_const;
+  n.n_atoms = s->n_atoms; n.n_pad = s->n_pad; n.n_slices = s->n_slices; n.nt0 = L.p0.nt; n.nt1 = L.p1.nt;
+  n.no0 = (s->hp.mul0 + 31) / 32; n.no1 = (s->hp.mul1 + 31) / 32;
+  n.mul0 = s->hp.mul0; n.mul1 = s->hp.mul1; n.in0 = L.in0; n.in1 = L.in1; n.XSin = XSin;
+  ProfScope ps(s, JAMUN_PROF_NODE, st);
+  launch_node_wide(n, st);
+}
+
 void run_layer(jamun_sampler* s, size_t l, const float* x_in, int XSin, float* x_out, hipStream_t st) {
+  if (s->wide) {
+    run_layer_wide(s, l, x_in, XSin, x_out, st);
+    return;
+  }
   LayerDev& L = s->layers[l];
   const float* h_l = s->h + (s->h_batched ? l * s->h_stride : 0);
   if (!s->h_batched) {  // (batches above 4 GiB of activations: one layer's radial MLP at a time)
@@ -1517,7 +1629,8 @@ void forward(jamun_sampler* s, float* y, float* xhat, float* score, hipStream_t 
   hd.cS = s->hp.act_gate_const; hd.n_atoms = s->n_atoms; hd.mul0 = s->hp.mul0; hd.mul1 = s->hp.mul1;
   {
     ProfScope ps(s, JAMUN_PROF_HEAD, st);
-    launch_head(hd, st);
+    if (s->wide) launch_head_wide(hd, st);
+    else launch_head(hd, st);
     if (next_pre)  // walk: this iteration's finalize and the next iteration's geometry in one launch
       launch_finalize_geom(y, s->yc, s->g, s->ptr, s->n_graphs, s->c_skip, s->c_out, s->sigma * s->sigma, s->hp.mean_center, s->tmp, xhat, score, post,
                            s->c_in, s->r2, s->S, s->bond_in_ptr, s->bond_in_src, s->deg, s->esrc, s->egeo, s->epair, *next_pre, st);
@@ -1751,9 +1864,12 @@ int jamun_version(void) { return 6; }
 int jamun_model_create(const jamun_hparams* hp, const jamun_tensor* tensors, int32_t n_tensors, jamun_model** out) {
   return guarded([&] {
     if (!hp || !out || (!tensors && n_tensors > 0)) throw Err(JAMUN_ERR_INVALID, "null argument");
-    if (hp->edge_attr_dim != 64) throw Err(JAMUN_ERR_INVALID, "only edge_attr_dim = 64 is supported");
+    // (Conv models of any width and radial size run: outside the compiled-width kernels' envelope on the wide path, jamun_wide.hip;
+    // SeparableConv keeps its envelope)
+    if (hp->separable && hp->edge_attr_dim != 64) throw Err(JAMUN_ERR_INVALID, "only edge_attr_dim = 64 is supported");
+    if (hp->edge_attr_dim < 2) throw Err(JAMUN_ERR_INVALID, "edge_attr_dim must be at least 2 (one bonded and one radial feature)");
     if (hp->mul0 < 1 || hp->mul1 < 0 || hp->n_layers < 0) throw Err(JAMUN_ERR_INVALID, "bad irreps_hidden / n_layers");
-    if ((hp->mul0 + hp->mul1 + 31) / 32 > 5 || (hp->mul1 + 31) / 32 > 2)
+    if (hp->separable && ((hp->mul0 + hp->mul1 + 31) / 32 > 5 || (hp->mul1 + 31) / 32 > 2))
       throw Err(JAMUN_ERR_INVALID, "irreps_hidden too wide for the compiled conv tiles (mul0 + mul1 <= 160, mul1 <= 64)");
     if (hp->mul1 == 0) throw Err(JAMUN_ERR_INVALID, "irreps_hidden needs at least one 1e channel (output is 1x1e)");
     if (hp->emb_dim[0] != hp->emb_dim[1])
@@ -1807,8 +1923,16 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
     s->n_pad = ((topo->n_atoms + 31) / 32) * 32;
     s->XS = hp.mul0 + 3 * hp.mul1;
     s->n_emb = hp.emb_dim[0] + hp.emb_dim[1] + hp.emb_dim[2] + hp.emb_dim[3];
-    if (s->n_emb > 224 || hp.mul0 + 3 * hp.mul1 > 224 || hp.mul0 + hp.mul1 > 160 || hp.mul1 > 32)
-      throw Err(JAMUN_ERR_INVALID, "irreps too wide for the node-update tiling (embedding <= 224, hidden <= 160 channels, <= 32 vectors)");
+    {
+      // Conv models outside the envelope of the compiled-width kernels take the wide path (jamun_wide.hip); every model inside it selects
+      // exactly the kernels it selected before the wide path existed
+      const bool outside = hp.edge_attr_dim != 64 || (hp.mul0 + hp.mul1 + 31) / 32 > 5 || (hp.mul1 + 31) / 32 > 2 || s->n_emb > 224 ||
+                           hp.mul0 + 3 * hp.mul1 > 224 || hp.mul0 + hp.mul1 > 160 || hp.mul1 > 32;
+      s->wide = outside && !hp.separable;
+      if (outside && !s->wide)
+        throw Err(JAMUN_ERR_INVALID, "irreps too wide for the node-update tiling (embedding <= 224, hidden <= 160 channels, <= 32 vectors)");
+    }
+    const bool wide = s->wide;
     const int N = topo->n_atoms, W = topo->n_graphs;
     // ---- normalisation factors in fp32, op for op as Denoiser.normalization_factors (denoiser.py:116-136,177-178)
     {
@@ -1852,7 +1976,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
       const std::pair<const char*, int (*)()> lds_attr[] = {{"k_conv", conv_set_max_lds}, {"k_node_update", node_update_set_max_lds},
                                                             {"k_conv_init_v", conv_initv_set_max_lds}, {"k_conv_dg", conv_dg_set_max_lds},
                                                             {"jamun_conv_mf.hip", conv_mf_set_max_lds}, {"jamun_conv_ml.hip", conv_ml_set_max_lds},
-                                                            {"jamun_sepconv.hip", sep_conv_set_max_lds}};
+                                                            {"jamun_sepconv.hip", sep_conv_set_max_lds}, {"jamun_wide.hip", conv_wide_set_max_lds}};
       for (auto& f : lds_attr)
         if (f.second() != 0)
           throw Err(JAMUN_ERR_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + f.first + ": " + hipGetErrorString(hipGetLastError()));
@@ -1920,7 +2044,8 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
           uid[i] = it->second;
         }
       }
-      s->layers.push_back(build_layer(*m, "initial_projector", ib, ones, s->n_slices, &uniq, s->n_emb, false, &xe_host));
+      if (wide) s->layers.push_back(build_layer(*m, "initial_projector", ib, ones, s->n_slices, nullptr, 0, false, nullptr, true));
+      else s->layers.push_back(build_layer(*m, "initial_projector", ib, ones, s->n_slices, &uniq, s->n_emb, false, &xe_host));
       s->n_uniq = (int)(uniq.size() / (size_t)std::max(s->n_emb, 1));
       if (s->layers.back().tt2 || s->layers.back().tabw) s->atom_uid = dev_upload(uid);
     }
@@ -1928,7 +2053,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
       std::vector<InBlock> ib = {{hp.mul0, 0, 0, 0}, {hp.mul1, 1, hp.mul0, hp.mul0}};
       const std::string li = std::to_string(l);
       std::vector<double> sc = noise_mlp(*m, "noise_scalings." + li + ".scale_predictor", hp.mul0 + hp.mul1, c_noise);
-      LayerDev L = build_layer(*m, "layers." + li, ib, sc, s->n_slices, nullptr, 0, /*pack_dg=*/!tn.no_dg);
+      LayerDev L = build_layer(*m, "layers." + li, ib, sc, s->n_slices, nullptr, 0, /*pack_dg=*/!tn.no_dg && !wide, nullptr, wide);
       std::vector<double> wm = noise_mlp(*m, "skip_connections." + li + ".weights.scale_predictor", hp.mul0 + hp.mul1, c_noise);
       std::vector<float> mix(wm.size());
       for (size_t i = 0; i < wm.size(); ++i) mix[i] = (float)(1.0 / (1.0 + std::exp(-wm[i])));
@@ -1964,7 +2089,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
     const int n_k = hp.edge_attr_dim + 1;
     // ---- destination-grouped VALU-forming kernel for the hidden layers (jamun_conv_dg.hip): own tile plan, larger spans
     {
-      bool ok = !tn.no_dg && hp.n_layers > 0 && s->S <= 64 && (int64_t)N * s->S < (int64_t)0x7fffffff;
+      bool ok = !tn.no_dg && !wide && hp.n_layers > 0 && s->S <= 64 && (int64_t)N * s->S < (int64_t)0x7fffffff;
       for (size_t l = 1; l < s->layers.size(); ++l) ok = ok && s->layers[l].dg.wx != nullptr;
       // Source rows resident in LDS for the whole segment when the largest molecule fits the resident budget (~80 rows);
       // otherwise the alternating-residency mode of the kernel (rows re-staged per phase: spans up to ~170 rows), and only
@@ -2209,7 +2334,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
         cmask_all.insert(cmask_all.end(), L.cmask_h.begin(), L.cmask_h.end());
       }
       s->w1r_all = dev_upload(w1r_all);
-      if (hp.edge_attr_dim == 64 && !tn.edge_h_fp32) {
+      if (hp.edge_attr_dim == 64 && !tn.edge_h_fp32 && !wide) {
         // f16x3 radial MLP (k_edge_h16): W1's radial part per layer scaled to the top of the f16 range and split hi + lo, as A fragments
         std::vector<float4> w1h;
         std::vector<float> isc;
@@ -2248,7 +2373,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
       }
       s->cmask_all = dev_upload(cmask_all);
       s->h_kstride = (NS + 63) & ~(size_t)63;
-      s->h_stride = s->h_kstride * JAMUN_HROWS;
+      s->h_stride = s->h_kstride * (wide ? (size_t)hp.edge_attr_dim + 1 : (size_t)JAMUN_HROWS);  // (H + 1 rows)
       s->h_batched = s->h_stride * s->layers.size() * sizeof(float) <= ((size_t)4 << 30);  // all layers' h~ at once, up to 4 GiB
       // (+ slack: k_conv_mf reads h~ at slot0 + p * stride without a bounds test; lanes past the last atom's slots read up to
       // 32 * S + 128 floats beyond the table and never use them)
@@ -2265,6 +2390,14 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
         if (L.sep.w2b) dw = std::max(dw, L.sep.n0 + L.sep.n1 + 3 * (L.sep.n0 + 2 * L.sep.n1));
       if (dw > 0) s->sep_D = dev_alloc<float>((size_t)N * dw);
     }
+    if (wide) {
+      int k0 = 8, k1 = 8;
+      for (auto& L : s->layers) { k0 = std::max(k0, L.K0w); k1 = std::max(k1, L.K1w); }
+      s->z0 = dev_alloc<float>((size_t)s->n_pad * k0);
+      s->z1 = dev_alloc<float>((size_t)3 * s->n_pad * k1);
+      HIPCHECK(hipMemset(s->z0, 0, sizeof(float) * (size_t)s->n_pad * k0));
+      HIPCHECK(hipMemset(s->z1, 0, sizeof(float) * (size_t)3 * s->n_pad * k1));
+    }
     s->g = dev_alloc<float>((size_t)N * 3);
     s->tmp = dev_alloc<float>((size_t)N * 3);
     s->xhat_buf = dev_alloc<float>((size_t)N * 3);
@@ -2276,7 +2409,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
     s->flop_ref_per_edge = 0;
     s->flop_exec = 0;
     for (auto& L : s->layers) {
-      s->flop_ref_per_edge += 2LL * 64 * 64 + 130LL * L.tp_numel;  // SURVEY.md §8 d (SeparableConv: tp_numel = the 336 depth-wise weights)
+      s->flop_ref_per_edge += 2LL * hp.edge_attr_dim * hp.edge_attr_dim + 2LL * (hp.edge_attr_dim + 1) * L.tp_numel;  // SURVEY.md §8 d (SeparableConv: tp_numel = the 336 depth-wise weights)
       if (s->dg_on && &L != &s->layers[0]) {
         // per (tile, k) in k_conv_dg: fp32 path 476 units of v_mfma_f32_32x32x2 (4096 FLOP); f16x3 path 150 v_mfma_f32_32x32x16_f16
         // (32768 FLOP: 50 groups of 16 inputs x 3 products) + 72 v_mfma_f32_16x16x32_f16 (16384 FLOP); + 60 fp32 units per (32 atoms, k)
@@ -2301,7 +2434,8 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
 // sampler restricted to the general kernels (k_conv, k_node_update, k_edge_h: fp32 MFMAs / vector ALUs, no host-planned tiles).  Node
 // features after every block and the network output must agree to 2e-5 of the block's largest feature (the parity tests' bound; the f16x3
 // kernels sit at 1e-6).  The opt-in reduced-precision mode (f16x1) is checked against its own bound, 2e-2.  SeparableConv has one
-// implementation and is not checked.  Cost: one general-kernel forward + the packing of its weights (cfg2: 0.3 s, once per sampler).
+// implementation and is not checked; neither is the wide path (jamun_wide.hip): it IS the general path for the models it serves (fp32
+// MFMAs / vector ALUs, no host-planned tiles), so it selects no specialised kernel and builds no second sampler.  Cost: one general-kernel forward + the packing of its weights (cfg2: 0.3 s, once per sampler).
 static void sampler_self_check(const jamun_model* m, float sigma, const jamun_topology* topo, jamun_sampler* s) {
   const bool special = s->dg_on || s->mfi_on || s->mfx_on || s->mlx_on || s->initv_on;
   if (!special) return;
@@ -2641,11 +2775,11 @@ int jamun_sampler_stats(jamun_sampler* s, jamun_stats* out, void* stream) {
     }
     out->edge_stride = s->S;
     out->n_slices = s->dg_on ? s->dg_n_slabs : s->n_slices;
-    out->conv_path = s->dg_on ? 2 : 0;
+    out->conv_path = s->wide ? 3 : s->dg_on ? 2 : 0;
     out->dg_mode = s->dg_on ? s->dg_mode : -1;
-    out->init_path = s->mlx_on ? 5 : s->mfx_on ? 4 : s->mfi_on ? 3 : s->initv_on ? 2 : 0;
+    out->init_path = s->wide ? 6 : s->mlx_on ? 5 : s->mfx_on ? 4 : s->mfi_on ? 3 : s->initv_on ? 2 : 0;
     out->dg_row_blocks = s->dg_on && s->dg_row_blocks ? 1 : 0;
-    out->dg_emu = s->dg_on ? (s->x1 ? 2 : s->dg_emu) : -1;
+    out->dg_emu = s->wide ? 0 : s->dg_on ? (s->x1 ? 2 : s->dg_emu) : -1;  // (the wide path: fp32 MFMAs, jamun_tuning.f16x1 ignored)
     out->conv_flop_exec_launch = (s->x1 && s->dg_mode == 4) ? s->conv_flop_exec_launch / 3 : s->conv_flop_exec_launch;
     if (s->dg_on && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0) {  // (block-sparse forming: counted by the kernel; mean over its launches so far)
       unsigned long long cnt = 0;

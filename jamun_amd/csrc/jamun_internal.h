@@ -363,6 +363,51 @@ struct HeadArgs {
   int n_atoms, mul0, mul1;
 };
 
+// ---- wide path (jamun_wide.hip): Conv models of any hidden width, radial size and embedding width (jamun_stats.conv_path 3)
+#define JAMUN_WIDE_KSUB0 4  // hidden units per k-subgroup, scalar-output rows (subgroups of 1..4)
+#define JAMUN_WIDE_KSUB1 2  // ... vector-output rows (subgroups of 1..2)
+
+struct EdgeHWideArgs {
+  const int* deg;
+  const int* esrc;
+  const float4* egeo;
+  int n_atoms, S;
+  int H, nr;               // radial-MLP hidden units (= edge_attr_dim) and radial basis functions ((H + 1) / 2)
+  int layer0;              // first block of the launch (blockIdx.y adds to it)
+  const float* w1r_all;    // [blocks][nr][H] radial part of W1
+  const float* cmask_all;  // [blocks][2][H] b1 + W1[:, bonded part] . E_bond[mask]
+  const float* mu;         // [nr] basis centres
+  float step;
+  float* h_all;            // block layer0 + y at h_all + y * h_layer_stride: [H + 1 rows][h_kstride]
+  size_t h_layer_stride, h_kstride;
+};
+
+struct NodeWideArgs {
+  const float* partial0;  // [n_slices][n_pad][nt0*32]
+  const float* partial1;  // [n_slices][n_pad][3][nt1*32]
+  const int* deg;
+  const float* x_in;      // [n_atoms][XSin]
+  float* x_out;           // [n_atoms][mul0+3*mul1]
+  float* z0;              // [n_pad][K0p]   [cL act(m0) | x_in scalars | 0]              (rows past n_atoms stay zero)
+  float* z1;              // [3][n_pad][K1p] [gate * m1 plane m | x_in vectors plane m | 0]
+  // [W_self ; W_skip] as MFMA B fragments, K permuted so that a lane's A operand is one float4 of a Z row:
+  // wn0 [nt0][K0p/8][64] float4, lane (c, hh), element st: row 8 g + 4 hh + st, column 32 t + c; wn1 [nt1][K1p/8][64]
+  const float4* wn0;
+  const float4* wn1;
+  int K0p, K1p;
+  const float* mix;       // [mul0+mul1] or nullptr (initial projector)
+  float cL, cS;
+  int n_atoms, n_pad, n_slices, nt0, nt1;  // (nt0 / nt1: column tiles of a slab row — the conv's, padded — not of the outputs)
+  int no0, no1;                            // output column tiles of the linear: ceil(mul0 / 32), ceil(mul1 / 32) (the tiles of wn0 / wn1)
+  int mul0, mul1, in0, in1, XSin;
+};
+void launch_edge_h_wide(const EdgeHWideArgs& a, int n_layers, hipStream_t st);
+int launch_conv_wide(const ConvArgs& a, int rc, int nt_all, hipStream_t st);  // (nt_all: column tiles of the packed weights / slab rows)
+int conv_wide_set_max_lds();
+size_t conv_wide_lds_bytes(int rc, int S);
+void launch_node_wide(const NodeWideArgs& a, hipStream_t st);
+void launch_head_wide(const HeadArgs& a, hipStream_t st);
+
 struct LangevinConsts {
   float u_half_delta;  // (float)(u * (delta/2))
   float half_delta;    // (float)(delta/2)
