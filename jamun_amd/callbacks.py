@@ -134,18 +134,21 @@ class SaveTrajectoryCallback:
         if self.write_dcd:
             save_dcd(self.filename_pred(label, index, "dcd"), frames)
 
-    def _raise_finished_writer_errors(self) -> None:
-        """A writer failure (disk full, permission, bad shape) must stop the run at the NEXT batch, not after the last one."""
-        still = []
+    def _finished_writer_error(self) -> Optional[BaseException]:
+        """A writer failure (disk full, permission, bad shape) must stop the run at the NEXT batch, not after the last one.  It is
+        returned, not raised: only rank 0 writes, and the other ranks learn of it in the gather (raising here would leave them waiting
+        in the gather's collectives)."""
+        still, error = [], None
         for fut in self._pending:
-            if fut.done():
-                fut.result()
-            else:
+            if not fut.done():
                 still.append(fut)
+            elif error is None:
+                error = fut.exception()
         self._pending = still
+        return error
 
     def on_after_sample_batch(self, sample: Sequence[dict], sampler):
-        self._raise_finished_writer_errors()
+        error = self._finished_writer_error()
         for s in sample:
             if s.get("dataset_label") not in self.datasets:
                 raise KeyError(f"sample dataset label {s.get('dataset_label')!r} has no dataset")
@@ -159,12 +162,15 @@ class SaveTrajectoryCallback:
             block = torch.stack([s[self.sample_key] for s in mine]).contiguous() if mine else None  # [chains_local, n, T, 3]
             # one block at a time through ONE reusable device receive buffer and ONE reusable pinned staging buffer; what the writer
             # thread (and self.chains) keep are pageable copies
-            blocks = dist.gather_ragged_to_host(block, dst=0, device=sampler.device, stager=self._stager, timings=self.gather_timings)
+            blocks = dist.gather_ragged_to_host(block, dst=0, device=sampler.device, stager=self._stager, timings=self.gather_timings,
+                                                error=error)
             if blocks is None:
                 continue
             start = self.num_chains_seen[label]
             self.num_chains_seen[label] = start + sum(int(b.shape[0]) for b in blocks)
             self._submit(self._write_batch, label, blocks, start)
+        if error is not None:  # (no label, so no gather to carry it)
+            raise error
 
     def _write_batch(self, label: str, blocks: List[np.ndarray], start: int) -> None:
         new = [c for b in blocks for c in b]
@@ -175,8 +181,15 @@ class SaveTrajectoryCallback:
             self._write_chain(label, "joined", np.concatenate(self.chains[label], axis=1))  # "b n t c -> n (b t) c"
 
     def _submit(self, fn, *args) -> None:
-        if not self.async_write:
-            fn(*args)
+        if not self.async_write:  # a failed synchronous write surfaces at the next batch too, through the same gather
+            from concurrent.futures import Future
+
+            fut = Future()
+            try:
+                fut.set_result(fn(*args))
+            except Exception as e:
+                fut.set_exception(e)
+            self._pending.append(fut)
             return
         if self._pool is None:
             from concurrent.futures import ThreadPoolExecutor

@@ -7,14 +7,18 @@ Accepts the reference's command-line form (``--config-dir``, ``experiment=...``,
 config keys.  Differences, all explicit: no wandb (``wandb_train_run_path`` must be null; use ``checkpoint_dir``),
 ``finetune_on_init`` must be null/false (training is out of scope), ``sampler.accelerator=cpu`` /
 ``trainer.accelerator=cpu`` is rejected (there is no CPU path).
+
+``sampler.devices`` (``jamun_amd.dist.resolve_devices``) asking for more than one GPU starts one rank per GPU, as the reference's
+``fabric.launch()`` does: the same command line runs in each rank with one shared ``run_key`` (`launch_plan`).
 """
 
 from __future__ import annotations
 
+import json
 import logging
 import os
 import sys
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -100,12 +104,34 @@ def compose(argv: List[str], cwd: Optional[str] = None) -> dict:
     return cfg
 
 
+def launch_plan(cfg: dict, argv: List[str], environ: Optional[dict] = None) -> Optional[Tuple[List[int], List[str]]]:
+    """``(devices, rank command)`` when ``jamun_sample`` must start one rank per device of ``sampler.devices``; ``None`` when this
+    process samples itself: ``auto``, one device, or already a rank of a launched job (``WORLD_SIZE`` set).  ``run_key`` (default
+    ``${now:...}``) is resolved once here and passed to every rank, so that all ranks write into one run directory."""
+    environ = os.environ if environ is None else environ
+    if "WORLD_SIZE" in environ:
+        return None
+    r = C.resolve(cfg, throw_on_missing=False)
+    smp = r.get("sampler") or {}
+    devices = dist.resolve_devices(smp.get("devices", "auto"), smp.get("num_nodes", 1))
+    if devices is None or len(devices) < 2:
+        return None
+    return devices, [sys.executable, "-m", "jamun_amd.cmdline", *argv, "++run_key=" + json.dumps(r["run_key"])]
+
+
 def main(argv: Optional[List[str]] = None):
     argv = list(sys.argv[1:] if argv is None else argv)
     logging.basicConfig(level=logging.INFO)
-    dist.init_process_group()
     cwd = os.getcwd()
     cfg = compose(argv, cwd)
+    plan = launch_plan(cfg, argv)
+    if plan is not None:  # this process makes no GPU call: each rank opens its own
+        devices, cmd = plan
+        log.info("sampler.devices: starting %d ranks on GPUs %s", len(devices), ",".join(map(str, devices)))
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # the ranks import this copy of the package
+        env = dict(os.environ, PYTHONPATH=os.pathsep.join(p for p in (root, os.environ.get("PYTHONPATH")) if p))
+        sys.exit(dist.launch_ranks(cmd, devices, env=env))
+    dist.init_process_group()
     head = C.resolve({k: cfg[k] for k in ("paths", "task_name", "run_group", "run_key")})
     run_dir = head["paths"]["run_path"]
     run_dir = run_dir if os.path.isabs(run_dir) else os.path.join(cwd, run_dir)

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import os
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, Iterable, List, Optional, Union
 
@@ -348,10 +349,14 @@ class SampleGraph(dict):
 class Sampler:
     """Host loop over sampling batches (``sampling/_sampler.py:15-98``) without Lightning Fabric.
 
-    One process per GPU: ``devices`` / ``strategy`` / ``num_nodes`` are accepted for config compatibility; rank and world
-    size come from ``torch.distributed`` when it is initialised (launch with ``torch.distributed.run``).  With
-    ``shard_walkers=True`` (extension; the reference replicates) the walker batch is split in contiguous blocks across
-    ranks and callbacks receive only the local walkers; see ``jamun_amd.dist``.
+    One process per GPU.  Rank and world size come from ``torch.distributed`` when it is initialised, else from the torchrun
+    environment.  The ranks are started by ``jamun_sample`` (one per entry of ``sampler.devices``), by
+    ``jamun_amd.dist.launch_ranks`` or by ``torch.distributed.run``; this class starts none.  ``devices`` takes the forms of
+    ``jamun_amd.dist.resolve_devices``.  Outside a launched job (``WORLD_SIZE`` unset) a request for more than one device raises
+    ``RuntimeError``, one device ``N = 1`` / ``[k]`` selects GPU 0 / ``k`` in this process, and ``"auto"`` keeps the GPU of
+    ``jamun_amd.dist.local_device``.  Inside a launched job ``devices`` is not enforced: each rank takes its own GPU.
+    ``strategy`` is accepted for config compatibility.  With ``shard_walkers=True`` (extension; the reference replicates) the
+    walker batch is split in contiguous blocks across ranks and callbacks receive only the local walkers; see ``jamun_amd.dist``.
     """
 
     def __init__(self, accelerator: str = "auto", strategy: str = "auto", devices: Any = "auto", num_nodes: int = 1,
@@ -382,10 +387,23 @@ class Sampler:
             raise RuntimeError("jamun_amd has no CPU path: sampler.accelerator must be gpu/cuda/auto")
         from . import dist
 
+        chosen = None
+        if "WORLD_SIZE" not in os.environ:
+            chosen = dist.resolve_devices(devices, num_nodes, count_devices=torch.cuda.device_count)
+            if chosen is not None and len(chosen) > 1:
+                raise RuntimeError(f"Sampler(devices={devices!r}) asks for {len(chosen)} GPUs, but this process is not part of a launched job "
+                                   "(WORLD_SIZE is unset) and samples on one GPU.  Start one rank per GPU with `jamun_sample ... "
+                                   "sampler.devices=N`, jamun_amd.dist.launch_ranks or torch.distributed.run.")
         self.rank, self.world_size = dist.rank_world()
         self.global_rank = self.rank
         self.is_global_zero = self.rank == 0
         self.device = dist.local_device()
+        if chosen is not None and self.device.type == "cuda":
+            n = torch.cuda.device_count()
+            if chosen[0] >= n:
+                raise ValueError(f"Sampler(devices={devices!r}) selects GPU {chosen[0]}, but {n} GPU(s) are visible")
+            self.device = torch.device("cuda", chosen[0])
+            torch.cuda.set_device(self.device)
         self.callbacks = list(callbacks) if callbacks is not None else []
         self.loggers = loggers
         self.shard_walkers = shard_walkers
