@@ -1,0 +1,266 @@
+// jamun_host.h — host-only declarations shared by jamun_pack.cpp (weight packing), jamun_plan.cpp (tile / work-list planning and
+// kernel selection) and jamun_api.cpp (sampler create, dispatch, the C ABI).  Not included by any .hip file.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/jamun_hip.h"
+#include "jamun_internal.h"
+
+struct Err : std::runtime_error {
+  int code;
+  Err(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
+
+#define HIPCHECK(expr)                                                                                 \
+  do {                                                                                                 \
+    hipError_t _e = (expr);                                                                            \
+    if (_e != hipSuccess) throw Err(JAMUN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+template <typename T>
+T* dev_alloc(size_t n) {
+  T* p = nullptr;
+  HIPCHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
+  return p;
+}
+template <typename T>
+T* dev_upload(const std::vector<T>& v) {
+  T* p = dev_alloc<T>(v.size());
+  if (!v.empty()) HIPCHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return p;
+}
+
+struct jamun_model {
+  jamun_hparams hp;
+  std::map<std::string, std::vector<float>> t;
+  const std::vector<float>& get(const std::string& name, int64_t numel = -1) const {
+    auto it = t.find(name);
+    if (it == t.end()) throw Err(JAMUN_ERR_MISSING, "missing checkpoint tensor: " + name);
+    if (numel >= 0 && (int64_t)it->second.size() != numel)
+      throw Err(JAMUN_ERR_INVALID, "tensor " + name + " has " + std::to_string(it->second.size()) +
+                                       " elements, expected " + std::to_string(numel));
+    return it->second;
+  }
+};
+
+// ---- packed weights of one layer (jamun_pack.cpp) ------------------------------------------------
+struct ConvProblemDev {
+  float4* wpack = nullptr;
+  int4* chunks = nullptr;
+  int* slice_ptr = nullptr;
+  int4* ublk = nullptr;
+  int* lane_xoff = nullptr;
+  int planes = 0, nt = 0, xw = 0;
+  int64_t K = 0;  // padded contraction depth
+};
+struct DgDev {
+  float4 *wx = nullptr, *wd = nullptr, *wv = nullptr, *wt = nullptr;  // null: the layer cannot use jamun_conv_dg.hip
+  float4* wxh = nullptr;  // f16x3 contraction: hi / lo planes of the scaled weights, one stream per (hidden unit, matrix wave)
+  float4* wth = nullptr;  // f16x3 T pre-pass: [k][8 groups of 16 inputs][hi, lo][64 lanes], A operand (lane (w', hh): inputs 16 g + 8 hh + j)
+  float4* wm = nullptr;   // jamun_conv_mf.hip: [k][4 matrix waves][40 blocks], K index permuted to the forming MFMA's accumulator layout
+  int sB = 0, sBt = 0, sTw = 0;
+  float hmax2 = 2.f;
+  // f16x3 balancing (build_layer): gx [216] 2^e_u per feature element (layout of a feature row), gT [128] the T pre-pass's input factors,
+  // cf0 [160] / cf1 [32] / cfT [32] the inverse column scales of the scalar / vector outputs / T
+  float *gx = nullptr, *gT = nullptr, *cf0 = nullptr, *cf1 = nullptr, *cfT = nullptr;
+  float4* wmt = nullptr;   // tail tiles (k_tail_contract): vector-output weights [k][24 blocks] under one column scale
+  float* cf1t = nullptr;   // ... its inverse [32]
+};
+struct SepDev {
+  float4* w2b = nullptr;  // null: not a SeparableConv layer
+  float *cfw = nullptr, *bias = nullptr, *wl0 = nullptr, *wl1 = nullptr;
+  int n0 = 0, n1 = 0, sH = 0;
+};
+struct LayerDev {
+  ConvProblemDev p0, p1;
+  DgDev dg;
+  SepDev sep;
+  std::vector<float> w1r_h, cmask_h;  // radial MLP first layer (uploaded for all layers together: jamun_sampler::w1r_all)
+  int tt_U = 0;  // distinct embedding rows of the tables below
+  float* tt2 = nullptr;  // the same table re-laid for k_conv_init_v: [k][U][192]
+  float4* tabw = nullptr;  // ... and scaled by 2^tab_sB, split hi + lo, as MFMA B fragments for k_conv_mfi (U <= 32): [k][24 blocks][64 lanes]
+  int tab_sB = 0, tab_ut = 0;
+  // k_conv_mfx (initial projector formed from the feature rows; batches with more than 32 distinct embedding rows)
+  float4* wx = nullptr;                  // [k][48 blocks] balanced, split weights (MfxArgs::wx)
+  unsigned *xph = nullptr, *xpl = nullptr;  // the embedding rows times channel factors and 2^x_sX, split, two atoms per word
+  int x_sX = 0;
+  float *xcf0 = nullptr, *xcf1 = nullptr;
+  float4 *wcat0 = nullptr, *wcat1 = nullptr;  // node update: [W_self ; W_skip] as MFMA fragments
+  int K0p = 0, K1p = 0;
+  float4 *wh0 = nullptr, *wh1 = nullptr;      // ... and balanced per row / column, split hi + lo for the f16x3 kernel (jamun_node.hip)
+  int K0h = 0, K1h = 0;
+  float *kga0 = nullptr, *kga1 = nullptr, *kgx = nullptr, *cg0 = nullptr, *cg1 = nullptr;  // its row (input) / column (output) powers of two
+  float* mix = nullptr;
+  float4 *wn0 = nullptr, *wn1 = nullptr;  // wide path (k_node_lin_wide): [W_self ; W_skip] with the K order of NodeWideArgs
+  int K0w = 0, K1w = 0;
+  int in0 = 0, in1 = 0, XSin = 0;
+  int64_t tp_numel = 0;
+};
+
+// ---- jamun_pack.cpp -----------------------------------------------------------------------------
+void free_dg(DgDev& d);
+void free_problem(ConvProblemDev& p);
+void pack8(const double (&v)[8], float4& hi, float4& lo);  // eight values, split into f16 hi + lo: one lane's fragment of an f16 MFMA in each plane
+std::vector<double> noise_mlp(const jamun_model& m, const std::string& prefix, int k, double c_noise);
+struct InBlock { int mul, l, xoff, ch0; };
+LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
+                     const std::vector<double>& s_in, int n_slices,
+                     const std::vector<float>* uniq_rows = nullptr, int row_len = 0, bool pack_dg = false,
+                     const std::vector<float>* all_rows = nullptr, bool wide = false);
+
+// The conv kernel family of the hidden layers and of the initial projector.  The enumerators carry the numbers jamun_stats documents for
+// conv_path / init_path (include/jamun_hip.h); SeparableConv has enumerators of its own here and is reported as 0 (jamun_sampler_stats).
+enum ConvPath {
+  CONV_GENERAL = 0,  // k_conv (jamun_conv.hip)
+  CONV_DG = 2,       // destination-grouped, on host-planned tiles: k_conv_dg / k_conv_mf / k_conv_ml by jamun_sampler::dg_mode
+  CONV_WIDE = 3,     // k_conv_wide (jamun_wide.hip): a Conv model outside the envelope of the compiled-width kernels
+  CONV_SEP = -1      // SeparableConv (jamun_sepconv.hip)
+};
+enum InitPath {
+  INIT_GENERAL = 0,
+  INIT_V = 2,    // k_conv_init_v (tiles / segments of the dg kernel)
+  INIT_MFI = 3,  // k_conv_mfi (mode 4 tiles, at most 32 distinct embedding rows)
+  INIT_MFX = 4,  // k_conv_mfx (mode 4 tiles, any number of distinct rows: formed from the feature rows)
+  INIT_MLX = 5,  // k_conv_mlx (mode 5 tiles: large spans)
+  INIT_WIDE = 6,
+  INIT_SEP = -1
+};
+
+struct jamun_sampler {
+  jamun_hparams hp;
+  jamun_tuning tune{};  // kernel-selection switches of jamun_sampler_create (all zero: defaults)
+  float sigma = 0;
+  int n_atoms = 0, n_graphs = 0, n_pad = 0, S = 0, n_slices = 8;
+  int XS = 0, n_emb = 0;
+  float c_in = 0, c_skip = 0, c_out = 0, r_cut = 0, r2 = 0, rb_step = 0;
+  // static device data
+  int *ptr = nullptr, *bond_in_ptr = nullptr, *bond_in_src = nullptr;
+  int n_tiles = 0;
+  // which kernels run (select_kernels): the hidden layers' conv and the initial projector's; jamun_stats reports these numbers
+  ConvPath conv_path = CONV_GENERAL;
+  InitPath init_path = INIT_GENERAL;
+  int initv_nbuf = 2;                 // INIT_V: row buffers of k_conv_init_v in LDS
+  int* atom_uid = nullptr;            // [n_atoms] index of the atom's distinct (scaled) embedding row
+  // destination-grouped VALU-forming conv kernel (jamun_conv_dg.hip; hidden layers): own tile plan (larger source spans)
+  bool dg_row_blocks = false;
+  int dg_mode = 0;  // 0 two-phase resident, 1 alternating residency, 2 single phase (see jamun_sampler_create)
+  int dg_emu = 1;   // 1: f16x3 contraction (three f16 MFMAs per fp32 product); 0 (jamun_tuning.dg_fp32): v_mfma_f32_32x32x2_f32; stats report 2 for the opt-in f16x1 mode (s->x1)
+  int dg_RS = 0, dg_grid = 0, dg_max_segs = 0, dg_n_slabs = 0, dg_n_tiles = 0;
+  int dg_ng = 1, dg_seg_cost_tenths = 0;  // k-slices and segment cost the work lists were cut with (jamun_debug_segments)
+  int2 *dg_tile_atoms = nullptr, *dg_tile_span = nullptr;
+  int4* dg_segs = nullptr;
+  int* dg_atom_nslab = nullptr;
+  float* sep_D = nullptr;  // SeparableConv: [n_atoms][K0 + 3 K1] per-destination sums of the layer at hand
+  int cus = 1;
+  float* dg_T = nullptr;  // [n_k][n_atoms][32] pre-pass product of a hidden layer (k_tprod), reused by every layer
+  int dg_tstride = 0;     // mode 4 (jamun_conv_mf.hip): dg_T is [n_k][32][dg_tstride], transposed
+  // tail tiles of the mode-4 plan (tiles with few destinations): formed with the hidden unit in the column index and contracted 32 gathered
+  // destinations at a time (k_tail_form / k_tail_contract) instead of as whole tiles of k_conv_mf; the initial projector keeps them as tiles
+  int n_tail_tiles = 0, n_tail = 0, tail_runs = 0;
+  int mf_nks = 4;  // forming K-steps of k_conv_mf (3: every whole tile's sources lie in the first 48 rows of its window)
+  int x1 = 0;         // 1: reduced-precision hidden-layer conv (jamun_tuning.f16x1) — honoured by k_conv_mf / k_conv_ml (dg_mode 4 / 5) only
+  int ml_window = 0;  // mode 5 (jamun_conv_ml.hip): source rows of the instantiation (96, 128, 168)
+  unsigned long long* ml_count = nullptr;  // device: v_mfma_f32_32x32x16_f16 executed by k_conv_ml since create (depends on the occupied source blocks)
+  int64_t ml_launches = 0;                 // ... over this many launches
+  int4* tail_tiles = nullptr;
+  int* tail_atom = nullptr;
+  float* tail_scale = nullptr;
+  float4* tail_P = nullptr;
+  int4* init_segs = nullptr;   // segment lists of the initial projector (ALL tiles) when the hidden layers' lists leave the tail tiles out
+  int* init_atom_nslab = nullptr;
+  int init_max_segs = 0, init_n_slabs = 0;
+  bool init_tail = false;      // the initial projector sends the tail tiles through k_tail_form_init / k_tail_contract as well
+  int n_uniq = 0;         // distinct (noise-scaled) embedding rows of the batch
+  int* mf_err = nullptr;  // device flag of k_conv_mf
+  int* mf_err_host = nullptr;  // pinned copy, refreshed behind every entry point that ran a forward (mf_err_fetch / mf_err_check)
+  float *x_emb = nullptr, *mu = nullptr;
+  float *z0 = nullptr, *z1 = nullptr;  // CONV_WIDE: node-update operands (NodeWideArgs::z0 / z1)
+  std::vector<LayerDev> layers;
+  float *w_gate = nullptr, *w_vec = nullptr, *w_out = nullptr;
+  // work buffers
+  float *w1r_all = nullptr, *cmask_all = nullptr;  // [layers][64][32], [layers][2][64]
+  float4* w1h_all = nullptr;                        // k_edge_h16: [layers][2 k-tiles][2 K-steps][hi, lo][64 lanes]
+  float* w1isc_all = nullptr;                       // [layers] 2^-(14 + sW)
+  size_t h_stride = 0, h_kstride = 0;  // per layer: [65 hidden rows][h_kstride edge slots]
+  bool h_batched = false, edges_built = false;
+  float *yc = nullptr, *h = nullptr, *partial0 = nullptr, *partial1 = nullptr, *g = nullptr, *tmp = nullptr;
+  float *xhat_buf = nullptr, *score_buf = nullptr, *psi = nullptr;
+  int *deg = nullptr, *esrc = nullptr;
+  int* epair = nullptr;  // k_geom's pair table (jamun_internal.h: JAMUN_EP_*), one word per edge slot
+  float4* egeo = nullptr;
+  std::vector<float*> x;  // per block output [n_atoms][XS]
+  unsigned long long* counter = nullptr;
+  int64_t flop_ref_per_edge = 0, flop_exec = 0, conv_flop_exec_launch = 0;
+  // optional per-kernel-class timing with HIP events on the launch stream (jamun_profile_*)
+  unsigned prof_mask = 0;  // bit c: record HIP events around launches of profile class c
+  int prof_every = 1;      // ... around every prof_every-th launch of the class (jamun_profile_sample)
+  int prof_seen[JAMUN_PROF_NCLASS] = {0};
+  std::vector<hipEvent_t> ev_pool;
+  std::vector<std::pair<int, std::pair<int, int>>> ev_used;  // (class, (begin, end))
+  size_t ev_next = 0;
+
+  ~jamun_sampler() {
+    hipFree(ptr); hipFree(bond_in_ptr); hipFree(bond_in_src); hipFree(x_emb); hipFree(mu);
+    hipFree(atom_uid); hipFree(w1r_all); hipFree(cmask_all); hipFree(w1h_all); hipFree(w1isc_all);
+    hipFree(epair); hipFree(dg_tile_atoms); hipFree(dg_tile_span); hipFree(dg_segs); hipFree(dg_atom_nslab); hipFree(dg_T); hipFree(mf_err); hipFree(ml_count);
+    hipFree(tail_tiles); hipFree(tail_atom); hipFree(tail_scale); hipFree(tail_P); hipFree(init_segs); hipFree(init_atom_nslab);
+    if (mf_err_host) hipHostFree(mf_err_host);
+    for (auto& L : layers) {
+      free_problem(L.p0); free_problem(L.p1); free_dg(L.dg);
+      hipFree(L.sep.w2b); hipFree(L.sep.cfw); hipFree(L.sep.bias); hipFree(L.sep.wl0); hipFree(L.sep.wl1);
+      hipFree(L.wcat0); hipFree(L.wcat1); hipFree(L.wh0); hipFree(L.wh1); hipFree(L.kga0); hipFree(L.kga1); hipFree(L.kgx); hipFree(L.cg0); hipFree(L.cg1); hipFree(L.mix); hipFree(L.tt2); hipFree(L.tabw);
+      hipFree(L.wx); hipFree(L.xph); hipFree(L.xpl); hipFree(L.xcf0); hipFree(L.xcf1); hipFree(L.wn0); hipFree(L.wn1);
+    }
+    hipFree(z0); hipFree(z1);
+    hipFree(w_gate); hipFree(w_vec); hipFree(w_out);
+    hipFree(yc); hipFree(h); hipFree(partial0); hipFree(partial1); hipFree(g); hipFree(tmp);
+    hipFree(xhat_buf); hipFree(score_buf); hipFree(psi); hipFree(deg); hipFree(esrc); hipFree(egeo);
+    for (float* p : x) hipFree(p);
+    hipFree(counter); hipFree(sep_D);
+    for (hipEvent_t e : ev_pool) hipEventDestroy(e);
+  }
+};
+
+// ---- jamun_plan.cpp -----------------------------------------------------------------------------
+void plan_tiles(const int32_t* ptr, const std::vector<int>& graph_of, int N, int cap, std::vector<int2>& t_atoms,
+                std::vector<int2>& t_span, std::vector<int>& t_chunk, int& n_chunks, int& span_max, bool& row_blocks);
+struct SegPlan {
+  std::vector<int4> segs;  // [cus][max_segs][2]
+  int max_segs = 1, n_slabs = 1;
+  std::vector<int> atom_nslab;
+};
+SegPlan plan_segments(int cus, int ng, int n_k, int N, const std::vector<int2>& t_atoms, const std::vector<int>& t_chunk, int n_chunks,
+                      const std::vector<int64_t>& tile_weight, const std::vector<char>* skip = nullptr, double seg_cost = 0.0);
+struct TilePlan {
+  std::vector<int2> atoms, span;  // per tile: {first destination atom, atoms}, {lo, hi} source atoms
+  std::vector<int> chunk;         // ... and its destination chunk (tiles of one chunk number their partial slabs jointly)
+  int n_chunks = 0, span_max = 0;
+  bool row_blocks = false;        // a molecule's sources were cut into row blocks
+};
+// What select_kernels decides; jamun_sampler_create uploads it and sizes the work buffers by it.  Below conv_path the fields are
+// meaningful for CONV_DG only.
+struct KernelPlan {
+  ConvPath conv_path = CONV_GENERAL;
+  InitPath init_path = INIT_GENERAL;
+  int dg_mode = 0, dg_emu = 1, dg_RS = 0;
+  TilePlan tiles;
+  int ng = 1;
+  double seg_cost = 0.0;
+  SegPlan segs, init_segs;     // work lists of the hidden layers; of the initial projector when it keeps lists of its own (own_init_segs)
+  bool own_init_segs = false, init_tail = false;
+  std::vector<int4> tail_tiles;  // tail tiles (mode 4): records, destinations, runs of hidden units, bytes of the parked operands
+  std::vector<int> tail_atom;
+  int tail_runs = 0;
+  size_t tail_P_bytes = 0;
+  int mf_nks = 4, ml_window = 0, initv_nbuf = 2;
+};
+ConvPath base_conv_path(const jamun_hparams& hp, int n_emb);
+KernelPlan select_kernels(const jamun_hparams& hp, const jamun_tuning& tn, const jamun_topology& topo, const std::vector<int>& graph_of, int nmax,
+                          int S, int cus, ConvPath base, const std::vector<LayerDev>& layers, int n_uniq, bool have_atom_uid);

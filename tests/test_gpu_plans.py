@@ -23,7 +23,7 @@ EXPECT = {  # (dg_mode, init_path) of the matrix-core variant
 
 
 def _weights(spans, dg_mode):
-    """The sampler's tile weights (jamun_api.cpp, jamun_sampler_create: 476 + 2 per 16 source rows, 24 in dg_mode 1)."""
+    """The sampler's tile weights (jamun_plan.cpp, select_kernels: 476 + 2 per 16 source rows, 24 in dg_mode 1)."""
     return 476 + (24 if dg_mode == 1 else 2) * ((spans[:, 1] - spans[:, 0] + 15) // 16)
 
 

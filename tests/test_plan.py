@@ -1,4 +1,4 @@
-"""CPU tests: the work-list planner of the destination-grouped conv kernels (``plan_segments`` in jamun_api.cpp, reached through
+"""CPU tests: the work-list planner of the destination-grouped conv kernels (``plan_segments`` in jamun_plan.cpp, reached through
 ``jamun_debug_plan_segments``) keeps its invariants under every plan the host can emit — k-slices over XCD groups (jamun_tuning.dg_kgroups),
 the segment cost (jamun_tuning.seg_cost_tenths), non-uniform tile weights, source row blocks sharing a destination chunk, skipped (tail) tiles.
 
