@@ -495,6 +495,7 @@ static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_t
     {
       const std::pair<const char*, int (*)()> lds_attr[] = {{"k_conv", conv_set_max_lds}, {"k_node_update", node_update_set_max_lds},
                                                             {"k_conv_init_v", conv_initv_set_max_lds}, {"k_conv_dg", conv_dg_set_max_lds},
+                                                            {"k_tprod_t", tprod_set_max_lds}, {"jamun_conv_tail.hip", conv_tail_set_max_lds},
                                                             {"jamun_conv_mf.hip", conv_mf_set_max_lds}, {"jamun_conv_ml.hip", conv_ml_set_max_lds},
                                                             {"jamun_sepconv.hip", sep_conv_set_max_lds}, {"jamun_wide.hip", conv_wide_set_max_lds}};
       for (auto& f : lds_attr)
@@ -1198,6 +1199,7 @@ int jamun_debug_stamps(unsigned long long* out8) {
   return guarded([&] {
     if (!out8) throw Err(JAMUN_ERR_INVALID, "null argument");
     HIPCHECK(hipDeviceSynchronize());
+    tprod_print_stamps();
     conv_dg_print_stamps();
     conv_initv_print_stamps();
     conv_mf_print_stamps();

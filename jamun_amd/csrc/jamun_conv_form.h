@@ -6,8 +6,7 @@
 #include <stdint.h>
 
 #include "jamun_internal.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "jamun_dev.h"
 
 #define A_ROW 33
 

@@ -27,9 +27,7 @@
 #include <stdint.h>
 
 #include "jamun_internal.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "jamun_dev.h"
 
 #define IV_WAVES 8
 #define IV_THREADS (64 * IV_WAVES)
@@ -37,38 +35,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define IV_ROW 192      // floats per staged table row: [u][4] scalar columns 4u..4u+3 | [u][2] (column 128+u, vector column u)
 #define IV_LROW 196     // LDS row stride in floats (784 B: consecutive rows start 4 banks apart; at 768 B every row starts on bank 0 and
                         // the two halves of a wave, which read different rows, collide)
-#define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define RFL(v) __builtin_amdgcn_readfirstlane(v)
 
 __device__ __forceinline__ f32x2 iv_pk_bhi(f32x2 a2, f32x2 b2, f32x2 c2) {  // (a.x b.y + c.x, a.y b.y + c.y)
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(c2) : "v"(a2), "v"(b2));
   return c2;
-}
-__device__ __forceinline__ float4 iv_lds_f4(int addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const f32x4 v = *(const __attribute__((address_space(3))) f32x4*)(unsigned)addr;
-  return make_float4(v.x, v.y, v.z, v.w);
-#else
-  (void)addr;
-  return make_float4(0.f, 0.f, 0.f, 0.f);
-#endif
-}
-__device__ __forceinline__ float2 iv_lds_f2(int addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const f32x2 v = *(const __attribute__((address_space(3))) f32x2*)(unsigned)addr;
-  return make_float2(v.x, v.y);
-#else
-  (void)addr;
-  return make_float2(0.f, 0.f);
-#endif
-}
-__device__ __forceinline__ int iv_lds_address(const void* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (int)(unsigned)(uintptr_t)(const __attribute__((address_space(3))) char*)p;
-#else
-  (void)p;
-  return 0;
-#endif
 }
 
 __host__ __device__ inline size_t iv_lds_floats(int rs, int pmax, int nbuf) {
@@ -159,7 +129,7 @@ __global__ __launch_bounds__(IV_THREADS) void k_conv_init_v(InitVArgs a) {
     // ---- per-wave edge tables (as the forming waves of k_conv_dg)
     const int fw = wave;
     const int h = lane >> 5, u = lane & 31;
-    const int rows_addr = iv_lds_address(rows_lds);
+    const int rows_addr = lds_addr(rows_lds);
     float evx[IV_NDP][2], evy[IV_NDP][2], evz[IV_NDP][2];
     int hidx[IV_NDP][2], hidx2[IV_NDP], P[IV_NDP];
     const bool two_pages = a.S > 32;
@@ -267,8 +237,8 @@ __global__ __launch_bounds__(IV_THREADS) void k_conv_init_v(InitVArgs a) {
 #pragma unroll
           for (int q = 0; q < IV_U; ++q) {
             c[q] = ta[IV_U * bb + q];       // c, c vx | c vy, c vz
-            x[q] = iv_lds_f4(J[q] + offa);  // s0 s1 | s2 s3
-            y[q] = iv_lds_f2(J[q] + offb);  // s4, v
+            x[q] = lds_f4(J[q] + offa);  // s0 s1 | s2 s3
+            y[q] = lds_f2(J[q] + offb);  // s4, v
           }
         };
         auto fm = [&](const float4 (&c)[IV_U], const float4 (&x)[IV_U], const float2 (&y)[IV_U]) {

@@ -30,7 +30,7 @@
 #include <type_traits>
 
 #include "jamun_internal.h"
-#include "jamun_mf_dev.h"
+#include "jamun_dev.h"
 
 #define ML_THREADS 512
 #if defined(ML_EXP)  // timing experiments, compile-time (-DML_EXP=bits; results are wrong): 1 no T term, 2 no coefficient build in the loops, 4 no forming
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(ML_THREADS) void k_conv_ml(MlArgs a) {
   const int tid0 = threadIdx.x, lane0 = tid0 & 63;
   const int wave = RFL(tid0 >> 6);
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  const float m1 = opaque_minus_one();  // (jamun_mf_dev.h: the split primitives as compiler-visible instructions)
+  const float m1 = opaque_minus_one();  // (jamun_split.h: the split primitives as compiler-visible instructions)
 
   for (int sgi = 0; sgi < a.max_segs; ++sgi) {
     const int4 sg0 = ld_const(a.segs + ((size_t)blockIdx.x * a.max_segs + sgi) * 2);
@@ -517,7 +517,6 @@ __global__ __launch_bounds__(ML_THREADS) void k_conv_ml(MlArgs a) {
         // T_k rows of the span (fp32, global, transposed by the pre-pass: MfArgs::Tt): lane (w' = r, hh) needs T[j][w'], j = 16 b + 8 hh .. + 7, of
         // every occupied block — two 16-byte buffer loads per block, a ring of four blocks in flight (the first four of a hidden unit are
         // requested during the previous unit's build)
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
         const int tvo = (r * a.t_stride + s_base + 8 * hh) * 4;  // this lane's byte offset inside the [32 w'][t_stride] table of a hidden unit
         constexpr int TD = NKS < 8 ? NKS : 8;  // blocks of T in flight: all of a hidden unit's up to eight occupied blocks, requested behind the previous unit's build
         f32x4 tq[TD][2];

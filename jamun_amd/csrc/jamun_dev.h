@@ -1,15 +1,22 @@
-// Device helpers shared by the matrix-formed conv kernels (jamun_conv_mf.hip, jamun_conv_ml.hip): f16x3 split primitives, LDS / constant
-// address-space loads, power-of-two scales, the MFMA wrappers.
+// jamun_dev.h — THE device helpers of every kernel file of the library (one definition each): the vector typedefs, the MFMA wrappers, the
+// f16x3 product macros, readfirstlane, the LDS barrier, absolute-address LDS accesses and constant address-space loads, power-of-two scales.
+// The f16x3 split primitives themselves are jamun_split.h (included here).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "jamun_split.h"
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
+#define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+#define MFMA16H(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
 #define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
 // one f16x3 product: lo hi + hi lo + hi hi (fp32 accumulate; the lo lo term is below 2^-24 of the product)
 #define M3(ACC, AH_, AL_, BH_, BL_)   \
@@ -29,9 +36,8 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ float4 lds_f4(int addr) {
+__device__ __forceinline__ float4 lds_f4(int addr) {  // ds_read_b128 from an absolute LDS address
 #if defined(__HIP_DEVICE_COMPILE__)
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   const f32x4 v = *(const __attribute__((address_space(3))) f32x4*)(unsigned)addr;
   return make_float4(v.x, v.y, v.z, v.w);
 #else
@@ -39,9 +45,17 @@ __device__ __forceinline__ float4 lds_f4(int addr) {
   return make_float4(0.f, 0.f, 0.f, 0.f);
 #endif
 }
+__device__ __forceinline__ float2 lds_f2(int addr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const f32x2 v = *(const __attribute__((address_space(3))) f32x2*)(unsigned)addr;
+  return make_float2(v.x, v.y);
+#else
+  (void)addr;
+  return make_float2(0.f, 0.f);
+#endif
+}
 __device__ __forceinline__ void lds_st4(int addr, const float4& v) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   *(__attribute__((address_space(3))) f32x4*)(unsigned)addr = f32x4{v.x, v.y, v.z, v.w};
 #else
   (void)addr; (void)v;
@@ -74,7 +88,7 @@ __device__ __forceinline__ int2 ld_const(const int2* p) {
   return *p;
 #endif
 }
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
+__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }  // 2^e, -126 <= e <= 127
 __device__ __forceinline__ int exp_above(float v) { return (int)((__float_as_uint(v) >> 23) & 0xffu) - 126; }  // v < 2^exp_above(v)
 __device__ __forceinline__ int clamp40(int s) { return max(-40, min(40, s)); }
 __device__ __forceinline__ int clamp100(int s) { return max(-100, min(100, s)); }

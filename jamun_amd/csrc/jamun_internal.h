@@ -1,4 +1,4 @@
-// Internal structures shared by jamun_kernels.hip (device code) and jamun_api.cpp (host runtime).
+// Internal structures shared by the kernel files (jamun_*.hip, device code and launchers) and the host runtime (jamun_api.cpp, jamun_plan.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -206,7 +206,7 @@ struct MfiArgs {
   int* err;
 };
 
-// tail tiles of k_conv_mf (k_tail_form + k_tail_contract in jamun_conv_mf.hip): tiles with few destinations, formed with the hidden unit in
+// tail tiles of k_conv_mf (k_tail_form + k_tail_contract in jamun_conv_tail.hip): tiles with few destinations, formed with the hidden unit in
 // the column index, parked, and contracted 32 gathered destinations at a time
 #define TAIL_NFT 23  // formed tiles of 32 channels per (destination, hidden unit): 0..3 scalar channels, 4 dot, 5 + 2 m x1[m], 6 + 2 m cross[m],
                      // 11 + 3 w + m scalar channels 32 w .. times v_m (in place of the T pre-pass)
@@ -243,8 +243,6 @@ struct TailArgs {
   float* partial1;
   int* err;
 };
-int launch_conv_tail(const TailArgs& a, hipStream_t st);
-int launch_conv_tail_init(const TailArgs& a, hipStream_t st);
 
 // initial projector formed from the feature rows (k_conv_mfx in jamun_conv_mf.hip): batches with many distinct embedding rows
 struct MfxArgs {
@@ -435,7 +433,43 @@ struct LangevinPost {
   LangevinConsts k{};
 };
 
-// launchers implemented in jamun_kernels.hip
+// jamun_conv.hip
+int launch_conv(const ConvArgs& a, int rc, int nt, hipStream_t st);
+int conv_set_max_lds();
+// jamun_conv_dg.hip
+int launch_conv_dg(const DgArgs& a, int grid, hipStream_t st);
+int conv_dg_set_max_lds();
+void conv_dg_print_stamps();
+size_t conv_dg_lds_bytes(int rs, int pmax, int mode, int emu);
+// jamun_tprod.hip
+void launch_tprod(const float* x, int XS, int n_atoms, int n_k, const float4* wt, const float4* wth, const float* gT, const float* cfT, float* T, int t_stride,
+                  hipStream_t st, bool no_tprod_t = false);  // (t_stride > 0 and f16x3 weights: k_tprod_t unless no_tprod_t)
+int tprod_set_max_lds();
+void tprod_print_stamps();  // (-DTP_TRACE builds: per-wave timeline of k_tprod_h / k_tprod_t)
+// jamun_conv_mf.hip
+int launch_conv_mf(const MfArgs& a, int grid, hipStream_t st);
+int launch_conv_mfi(const MfiArgs& a, int grid, hipStream_t st);
+int launch_conv_mfx(const MfxArgs& a, int grid, hipStream_t st);
+int conv_mf_set_max_lds();
+void conv_mf_print_stamps();
+size_t conv_mf_lds_bytes();
+// jamun_conv_tail.hip
+int launch_conv_tail(const TailArgs& a, hipStream_t st);
+int launch_conv_tail_init(const TailArgs& a, hipStream_t st);
+int conv_tail_set_max_lds();
+// jamun_conv_initv.hip
+int launch_conv_initv(const InitVArgs& a, int grid, hipStream_t st);
+int conv_initv_set_max_lds();
+void conv_initv_print_stamps();
+size_t conv_initv_lds_bytes(int rs, int pmax, int nbuf);
+// jamun_node.hip
+void launch_node_update(const NodeArgs& a, hipStream_t st);
+void launch_node_update_h(const NodeArgs& a, int cus, hipStream_t st);
+bool node_update_h_supported(const NodeArgs& a);
+size_t node_update_lds_bytes(const NodeArgs& a);
+int node_update_set_max_lds();
+void node_print_stamps();  // (-DNH_TRACE builds: per-wave timeline of k_node_update_h)
+// jamun_kernels.hip
 void launch_mean_center(const float* pos, const int* ptr, int n_graphs, float* out, hipStream_t st);
 void launch_radius_graph(const float* pos, const int* ptr, int n_graphs, float r2, int stride, int* nbr, int* deg,
                          hipStream_t st);
@@ -449,30 +483,6 @@ void launch_geom(float* y, const int* ptr, int n_graphs, float c_in, float r2, i
 void launch_edge_h(const int* deg, const int* esrc, const float4* egeo, int n_atoms, int S, const float* w1r_all,
                    const float* cmask_all, int n_layers, const float* mu, float step, float* h_all, size_t h_layer_stride,
                    size_t h_kstride, hipStream_t st, const float4* w1h = nullptr, const float* isc_all = nullptr);
-int launch_conv(const ConvArgs& a, int rc, int nt, hipStream_t st);
-int conv_set_max_lds();
-int launch_conv_dg(const DgArgs& a, int grid, hipStream_t st);
-int conv_dg_set_max_lds();
-void conv_dg_print_stamps();
-void node_print_stamps();  // (-DNH_TRACE builds: per-wave timeline of k_node_update_h)
-void conv_initv_print_stamps();
-void conv_mf_print_stamps();
-size_t conv_dg_lds_bytes(int rs, int pmax, int mode, int emu);
-void launch_tprod(const float* x, int XS, int n_atoms, int n_k, const float4* wt, const float4* wth, const float* gT, const float* cfT, float* T, int t_stride,
-                  hipStream_t st, bool no_tprod_t = false);  // (t_stride > 0 and f16x3 weights: k_tprod_t unless no_tprod_t)
-int launch_conv_mf(const MfArgs& a, int grid, hipStream_t st);
-int launch_conv_mfi(const MfiArgs& a, int grid, hipStream_t st);
-int launch_conv_mfx(const MfxArgs& a, int grid, hipStream_t st);
-int conv_mf_set_max_lds();
-size_t conv_mf_lds_bytes();
-int launch_conv_initv(const InitVArgs& a, int grid, hipStream_t st);
-int conv_initv_set_max_lds();
-size_t conv_initv_lds_bytes(int rs, int pmax, int nbuf);
-void launch_node_update(const NodeArgs& a, hipStream_t st);
-void launch_node_update_h(const NodeArgs& a, int cus, hipStream_t st);
-bool node_update_h_supported(const NodeArgs& a);
-size_t node_update_lds_bytes(const NodeArgs& a);
-int node_update_set_max_lds();
 void launch_head(const HeadArgs& a, hipStream_t st);
 void launch_finalize(const float* y, const float* yc, const float* g, const int* ptr, int n_graphs, float c_skip,
                      float c_out, float sigma2, int mean_center, float* tmp, float* xhat, float* score,

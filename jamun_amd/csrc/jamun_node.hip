@@ -1,6 +1,7 @@
-// jamun_node.hip — node update of a ConvBlock with both o3.Linear layers as f16x3 MFMAs.
+// jamun_node.hip — node update of a ConvBlock: k_node_update_h, both o3.Linear layers as f16x3 MFMAs (the default), and its fp32 twin
+// k_node_update (jamun_tuning.node_fp32; at the end of this file).
 //
-// Same arithmetic as k_node_update (jamun_kernels.hip; src/jamun/e3tools/nn/_conv.py:117, _gate.py:53-64, _interaction.py:26-30,
+// k_node_update_h: same arithmetic as k_node_update (src/jamun/e3tools/nn/_conv.py:117, _gate.py:53-64, _interaction.py:26-30,
 // model/noise_conditioning.py:69-73): sum the partial slabs of the conv (fixed order), mean over the in-edges, leaky-relu / sigmoid gate,
 // out = [act | x_in] . [W_self ; W_skip] (one contraction per irrep block), noise-conditional skip mix.  What changes is the shape:
 //   * phase 1 works on 16-byte pieces (16 threads per atom; 19 loads per thread instead of 62) and writes the Linear inputs ROW-major
@@ -19,16 +20,11 @@
 #include <stdio.h>
 
 #include "jamun_internal.h"
-#include "jamun_split.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+#include "jamun_dev.h"
 
 #define NH_T 512
 #define NH_S 3  // partial slabs fetched at once (more are summed in a loop)
 #define NH_W 8  // K-steps of weight blocks in flight per wave (the first NH_W are requested before phase 1)
-#define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
-#define RFL(v) __builtin_amdgcn_readfirstlane(v)
 
 #ifdef NH_TRACE  // per-wave timeline of every workgroup (diagnostic builds): [workgroup * 8 + wave][stamp]
 __device__ unsigned long long g_nhtrace[2400][8];
@@ -43,7 +39,6 @@ __device__ unsigned long long g_nhtrace[2400][8];
 
 namespace {
 
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
 __device__ __forceinline__ int scale_of(float mx) {  // largest magnitude -> [2^13, 2^14)
   int s = 0;
   if (mx > 0.f) s = 14 - ((int)((__float_as_uint(mx) >> 23) & 0xffu) - 126);
@@ -481,4 +476,214 @@ void launch_node_update_h(const NodeArgs& a, int cus, hipStream_t st) {
   else if (lr) hipLaunchKernelGGL((k_node_update_h<true, false>), dim3(grid), dim3(NH_T), lds, st, a);
   else if (fx) hipLaunchKernelGGL((k_node_update_h<false, true>), dim3(grid), dim3(NH_T), lds, st, a);
   else hipLaunchKernelGGL((k_node_update_h<false, false>), dim3(grid), dim3(NH_T), lds, st, a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// node update: sum the K-slice partials (fixed order), mean over in-edges, gate, self-interaction
+// Linear, skip Linear, noise-conditional skip mix.
+// (src/jamun/e3tools/nn/_conv.py:117, _gate.py:53-64, _interaction.py:26-30, model/noise_conditioning.py:69-73)
+// ------------------------------------------------------------------------------------------------
+// One workgroup = 32 atoms, 8 waves.  Phase 1 (all threads) builds the two Linear inputs TRANSPOSED in LDS
+// ([K][33]: lane = atom, conflict-free): scalars [act(m0) | x_in scalars], per vector plane [gate * m1 | x_in vectors].
+// Phase 2 runs both o3.Linear layers (self-interaction + skip, concatenated along K) on the matrix cores:
+// one job per wave: scalar output tile nt (32 columns) or one vector plane.  Weights are host-packed
+// 16-byte fragments in MFMA operand order (4 consecutive K-steps of one lane).
+#define NU_LD 33
+#define NU_T 512  // threads per workgroup
+#define NU_U 5    // 32-column tiles of the scalar rows per thread (nt0 <= 5)
+#define NU_X 7    // 32-column tiles of the input features per thread (XSin <= 224)
+#define NU_S 3    // partial slabs fetched at once (more are summed in a loop)
+#define NU_V 6    // (atom, plane) rows per thread: 32 atoms x 3 planes / 16 rows per pass (nt1 == 1)
+__global__ __launch_bounds__(NU_T) void k_node_update(NodeArgs a) {
+  extern __shared__ float sm[];
+  const int G0 = a.mul0 + a.mul1;
+  const int K0 = a.K0p, K1 = a.K1p;                 // padded contraction depths (multiples of 8)
+  float* __restrict__ A0 = sm;                      // [K0][33]
+  float* __restrict__ A1 = A0 + K0 * NU_LD;         // [3][K1][33]
+  float* __restrict__ s_gate = A1 + 3 * K1 * NU_LD; // [32][mul1]
+  const int n0 = blockIdx.x * 32;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 31, hh = lane >> 5;
+  const int w0 = a.nt0 * 32;  // padded row width of partial0
+  const int w1 = a.nt1 * 32;
+  const int ns_max = a.atom_nslab ? a.max_slabs : a.n_slices;
+  __shared__ int s_ns[32];
+  __shared__ float s_deg[32];
+  if (tid < 32) {
+    const int i = n0 + tid;
+    s_ns[tid] = i < a.n_atoms ? (a.atom_nslab ? a.atom_nslab[i] : a.n_slices) : 0;
+    const int d = i < a.n_atoms ? a.deg[i] : 1;
+    s_deg[tid] = (float)(d < 1 ? 1 : d);
+  }
+  __syncthreads();
+  // Thread -> element maps without integer division: a wave row of 32 lanes covers 32 consecutive columns (one 128-byte
+  // segment) of one atom; 16 rows per pass.  All global loads of phase 1 are issued before the first use.
+  const int col = tid & 31, row = tid >> 5;  // row < 16
+  // ---- vector-row slab sums: 96 (atom, plane) rows x 32 channels (nt1 == 1)
+  // The first NU_S slabs are fetched unconditionally (slab index clamped, result masked) so that all their loads are in
+  // flight together; a loop over s would wait for slab s before asking for slab s+1.  Summation order stays s = 0, 1, ...
+  float mv[NU_V];
+  {
+    float lv[NU_S][NU_V];
+#pragma unroll
+    for (int s = 0; s < NU_S; ++s)
+#pragma unroll
+      for (int u = 0; u < NU_V; ++u) {
+        const int rr = row + 16 * u, il = rr / 3;  // rr = il * 3 + plane
+        const int sc = s < s_ns[il] ? s : 0;
+        lv[s][u] = a.partial1[((size_t)sc * a.n_pad + n0) * 3 * w1 + rr * w1 + col];
+      }
+#pragma unroll
+    for (int u = 0; u < NU_V; ++u) {
+      const int rr = row + 16 * u, il = rr / 3;
+      mv[u] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NU_S; ++s) mv[u] += s < s_ns[il] ? lv[s][u] : 0.f;
+    }
+  }
+  for (int s = NU_S; s < ns_max; ++s) {
+#pragma unroll
+    for (int u = 0; u < NU_V; ++u) {
+      const int rr = row + 16 * u, il = rr / 3;
+      if (s < s_ns[il]) mv[u] += a.partial1[((size_t)s * a.n_pad + n0) * 3 * w1 + rr * w1 + col];
+    }
+  }
+  // ---- scalar-row slab sums: 32 atoms x w0 columns
+  float m0[2][NU_U];
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const int il = row + 16 * v;
+    float ls[NU_S][NU_U];
+#pragma unroll
+    for (int s = 0; s < NU_S; ++s) {
+      const int sc = s < s_ns[il] ? s : 0;
+#pragma unroll
+      for (int u = 0; u < NU_U; ++u) ls[s][u] = u < a.nt0 ? a.partial0[((size_t)sc * a.n_pad + n0 + il) * w0 + col + 32 * u] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < NU_U; ++u) {
+      m0[v][u] = 0.f;
+#pragma unroll
+      for (int s = 0; s < NU_S; ++s) m0[v][u] += s < s_ns[il] ? ls[s][u] : 0.f;
+    }
+  }
+  for (int s = NU_S; s < ns_max; ++s) {
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+      const int il = row + 16 * v;
+#pragma unroll
+      for (int u = 0; u < NU_U; ++u) {
+        const int w = col + 32 * u;
+        if (u < a.nt0 && s < s_ns[il]) m0[v][u] += a.partial0[((size_t)s * a.n_pad + n0 + il) * w0 + w];
+      }
+    }
+  }
+  // ---- input features
+  float xv[2][NU_X];
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const int il = row + 16 * v;
+#pragma unroll
+    for (int u = 0; u < NU_X; ++u) {
+      const int c = col + 32 * u;
+      xv[v][u] = (c < a.XSin && n0 + il < a.n_atoms) ? a.x_in[(size_t)(n0 + il) * a.XSin + c] : 0.f;
+    }
+  }
+  // ---- phase 1a: mean over in-edges, activation / gate
+#pragma unroll
+  for (int v = 0; v < 2; ++v) {
+    const int il = row + 16 * v;
+#pragma unroll
+    for (int u = 0; u < NU_U; ++u) {
+      const int w = col + 32 * u;
+      if (u >= a.nt0 || w >= G0) continue;
+      const float val = m0[v][u] / s_deg[il];
+      if (w < a.mul0) A0[w * NU_LD + il] = a.cL * (val > 0.f ? val : 0.01f * val);
+      else s_gate[il * a.mul1 + (w - a.mul0)] = a.cS / (1.f + expf(-val));
+    }
+    // x_in: scalars extend the scalar K range, vectors extend each plane's K range; pad rows are zero
+#pragma unroll
+    for (int u = 0; u < NU_X; ++u) {
+      const int c = col + 32 * u;
+      if (c >= a.XSin) continue;
+      if (c < a.in0) A0[(a.mul0 + c) * NU_LD + il] = xv[v][u];
+      else {
+        const int uu = (c - a.in0) / 3, mm = (c - a.in0) - 3 * uu;
+        A1[(mm * K1 + a.mul1 + uu) * NU_LD + il] = xv[v][u];
+      }
+    }
+  }
+  for (int idx = tid; idx < (K0 - a.mul0 - a.in0) * 32; idx += NU_T) A0[(a.mul0 + a.in0 + (idx >> 5)) * NU_LD + (idx & 31)] = 0.f;
+  for (int idx = tid; idx < 3 * (K1 - a.mul1 - a.in1) * 32; idx += NU_T) {
+    const int per = (K1 - a.mul1 - a.in1) * 32;
+    const int mm = idx >= 2 * per ? 2 : (idx >= per ? 1 : 0), rem = idx - mm * per;
+    A1[(mm * K1 + a.mul1 + a.in1 + (rem >> 5)) * NU_LD + (rem & 31)] = 0.f;
+  }
+  __syncthreads();
+  // ---- phase 1b: gated vectors
+#pragma unroll
+  for (int u = 0; u < NU_V; ++u) {
+    const int rr = row + 16 * u, il = rr / 3, mm = rr - 3 * il;
+    if (col < a.mul1) A1[(mm * K1 + col) * NU_LD + il] = (mv[u] / s_deg[il]) * s_gate[il * a.mul1 + col];
+  }
+  __syncthreads();
+  // ---- phase 2: out = [act | x_in] . [W_self ; W_skip] on the matrix cores, then the noise-conditional skip mix
+  const int XSo = a.mul0 + 3 * a.mul1;
+  const int nts = (a.mul0 + 31) >> 5, nsg0 = K0 >> 3, nsg1 = K1 >> 3;
+#if defined(NU_EXP) && (NU_EXP & 2)
+  if (a.mix) return;
+#endif
+  for (int job = wave; job < nts + 3; job += NU_T / 64) {
+    const bool scalar = job < nts;
+    const int nsg = scalar ? nsg0 : nsg1;
+    const float4* __restrict__ wp = (scalar ? a.wcat0 + (size_t)job * nsg0 * 64 : a.wcat1) + lane;
+    const float* __restrict__ ap = (scalar ? A0 : A1 + (job - nts) * K1 * NU_LD) + hh * NU_LD + r;
+    f32x16 acc;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+    float4 ring[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ring[i] = wp[(i < nsg ? i : nsg - 1) * 64];
+    for (int sg = 0; sg < nsg; sg += 4) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (sg + i < nsg) {  // wave-uniform
+          const float4 w = ring[i];
+          if (sg + i + 4 < nsg) ring[i] = wp[(sg + i + 4) * 64];
+          const float* __restrict__ as = ap + 8 * (sg + i) * NU_LD;
+#if defined(NU_EXP) && (NU_EXP & 1)
+          continue;
+#endif
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[0], w.x, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[2 * NU_LD], w.y, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[4 * NU_LD], w.z, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[6 * NU_LD], w.w, acc, 0, 0, 0);
+        }
+      }
+    }
+    const int col = scalar ? job * 32 + r : r;                 // output channel within the irrep block
+    const bool col_ok = scalar ? col < a.mul0 : col < a.mul1;
+    const int o = scalar ? col : a.mul0 + 3 * col + (job - nts);  // column of x_out
+    const float mw = (a.mix && col_ok) ? a.mix[scalar ? col : a.mul0 + col] : 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int i = n0 + (q & 3) + 8 * (q >> 2) + 4 * hh;
+      if (col_ok && i < a.n_atoms) {
+        float v = acc[q];
+        if (a.mix) v = mw * a.x_in[(size_t)i * a.XSin + o] + (1.f - mw) * v;  // hidden layers: XSin == XSo, x_in is x_old
+        a.x_out[(size_t)i * XSo + o] = v;
+      }
+    }
+  }
+}
+
+size_t node_update_lds_bytes(const NodeArgs& a) {
+  return sizeof(float) * ((size_t)a.K0p * NU_LD + 3 * (size_t)a.K1p * NU_LD + 32 * (size_t)a.mul1);
+}
+void launch_node_update(const NodeArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(k_node_update, dim3(a.n_pad / 32), dim3(NU_T), node_update_lds_bytes(a), st, a);
+}
+int node_update_set_max_lds() {
+  return hipFuncSetAttribute((const void*)k_node_update, hipFuncAttributeMaxDynamicSharedMemorySize, JAMUN_MAX_DYN_LDS) ==
+                 hipSuccess ? 0 : -1;
 }

@@ -288,7 +288,7 @@ KernelPlan select_kernels(const jamun_hparams& hp, const jamun_tuning& tn, const
   for (size_t t = 0; t < weight.size(); ++t) weight[t] = 476 + (sel.dg_mode == 1 ? 24 : 2) * ((T.span[t].y - T.span[t].x + 15) / 16);
   // Tail tiles (mode 4): a tile with at most 8 destinations costs k_conv_mf a whole tile per hidden unit (a 33-atom molecule cuts into
   // 32 + 1: twice the work of a 32-atom one).  They leave the hidden layers' segment lists and go through k_tail_form /
-  // k_tail_contract (jamun_conv_mf.hip); worth two more launches per layer when they are at least 4 and 3 % of the tiles.
+  // k_tail_contract (jamun_conv_tail.hip); worth two more launches per layer when they are at least 4 and 3 % of the tiles.
   std::vector<char> is_tail(T.atoms.size(), 0);
   if (sel.dg_mode == 4 && !tn.no_tail && layers.size() > 1 && layers[1].dg.wmt) {
     std::vector<int4> tt;

@@ -24,25 +24,12 @@
 #include <algorithm>
 
 #include "jamun_internal.h"
-#include "jamun_split.h"
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#define RFL(v) __builtin_amdgcn_readfirstlane(v)
-#define MFMA32H(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, (a)), __builtin_bit_cast(h8, (b)), (c), 0, 0, 0)
-#define M3(ACC, AH_, AL_, BH_, BL_)   \
-  ACC = MFMA32H(AL_, BH_, ACC);       \
-  ACC = MFMA32H(AH_, BL_, ACC);       \
-  ACC = MFMA32H(AH_, BH_, ACC)
+#include "jamun_dev.h"
 
 #define SF_THREADS 512
 #define SF_NCT 11                                  // column tiles of W2~
 #define SF_W2_BYTES (4 * SF_NCT * 2 * 1024)        // [4 K-steps][11 column tiles][hi, lo][64 lanes x 16 B]
 #define SF_LDS_BYTES (SF_W2_BYTES + 8 * 64 * 16 + 2 * 352 * 4)  // + slot records [8 waves][64] float4 + column factors and biases [2][352]
-
-namespace {
-__device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned)(e + 127) << 23); }
-}  // namespace
 
 __global__ __launch_bounds__(SF_THREADS) void k_sep_fused(SepArgs a) {
   extern __shared__ float4 sf_lds[];
