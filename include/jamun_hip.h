@@ -231,6 +231,27 @@ int jamun_node_linear(const float* x_dev, int32_t n_atoms, int32_t in0, int32_t 
  * same walk fed these draws as noise_dev. */
 int jamun_philox_normal(float* out_dev, int32_t n, uint64_t seed, uint32_t iteration, uint32_t first_atom, void* stream);
 
+/* ---- trajectory file encoders: device frames -> the bytes of jamun_amd/pdb.py's save_pdb / save_dcd --------------------------------
+ * Frames are fp32 in nanometres, addressed as xyz_dev[frame * frame_stride + atom * atom_stride + component] (strides in floats), so a
+ * contiguous [n, T, 3] chain (frame_stride 3, atom_stride 3 T) and a slice of a [T, sum N, 3] trajectory (frame_stride 3 sum N,
+ * atom_stride 3) are both read in place.  Caller-owned buffers, work queued on `stream`, no synchronisation.
+ *
+ * PDB: one model is the line "MODEL        {t}\n" (t unpadded) followed by a body that is constant per molecule apart from the 3 x 8
+ * coordinate characters of each atom (ATOM records, TER, CONECT block, ENDMDL).  body_dev [body_len] is that body as the host printed it
+ * once (pdb.pdb_model_template) and coord_off_dev [n_atoms] the ascending byte offset of each atom's x field in it (y and z follow).  The
+ * call writes models first_model .. first_model + n_frames - 1 back to back to out_dev; their exact size comes from the host-only
+ * jamun_pdb_models_nbytes (no device call), which is also how the caller sizes out_dev.  Each coordinate is printed as Python's
+ * f"{v:8.3f}" of v = fp32(x * 10).  A value that is not finite or needs more than 8 characters is written as "   0.000" and counted into
+ * *unencodable_dev (which the caller zeroes): a non-zero count means the caller must write that file on the host path. */
+int jamun_pdb_models_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames, int64_t* nbytes);
+int jamun_encode_pdb_models(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, int64_t first_model,
+                            const uint8_t* body_dev, int64_t body_len, const int32_t* coord_off_dev, uint8_t* out_dev, int64_t out_capacity,
+                            uint32_t* unencodable_dev, void* stream);
+/* DCD: per frame three Fortran records  int32 4 n_atoms | n_atoms x fp32 (coordinate * 10.0f, Angstrom) | int32 4 n_atoms  for X, Y, Z:
+ * n_frames * 3 * (4 n_atoms + 8) bytes, the coordinate block of a CHARMM DCD file behind its header.  out_dev must be 4-byte aligned. */
+int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, uint8_t* out_dev,
+                            int64_t out_capacity, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

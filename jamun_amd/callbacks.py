@@ -52,11 +52,22 @@ class SaveTrajectoryCallback:
     One deliberate deviation: the reference numbers the ``.pdb`` / ``.dcd`` files of a batch from the running chain count but
     restarts the ``.npy`` numbering at 0 in every batch (``enumerate(samples_np)`` at ``:81`` against ``start=self.num_chains_seen``
     at ``:89``), so its ``<i>.npy`` files of batch b overwrite those of batch b-1 and only ``joined.npy`` keeps everything.  Here all
-    three use the running index; ``npy_index_restarts_per_batch=True`` reproduces the reference's files exactly."""
+    three use the running index; ``npy_index_restarts_per_batch=True`` reproduces the reference's files exactly.
+
+    ``encode`` selects who turns frames into ``.pdb`` text and ``.dcd`` records.  ``"host"``: `pdb.save_pdb` / `pdb.save_dcd` on the
+    host copy of the batch, every file rewritten whole (``joined.*`` from every chain seen so far).  ``"device"``: the stacked
+    device block of the batch is kept until the writer thread has encoded it on the GPU (`traj_encode.DeviceTrajectoryEncoder`,
+    chunks of frames through fixed staging memory on one side stream) and ``joined.pdb`` / ``joined.dcd`` are EXTENDED by the new
+    chains' frames; the files are byte for byte those of ``"host"``.  ``"auto"`` (default) takes the device path when the sample
+    tensors are on a GPU, the native library loads and no process group is initialised (the multi-rank gather delivers host
+    blocks: it keeps the host path), else the host path.  ``.npy`` files are written from the host copy either way."""
 
     def __init__(self, datasets: Sequence, sample_key: str = "xhat_traj", output_dir: str = "sampler", write_pdb: bool = True,
                  write_dcd: bool = True, save_true_trajectory: bool = False, npy_index_restarts_per_batch: bool = False,
-                 async_write: bool = True, **_):
+                 async_write: bool = True, encode: str = "auto", **_):
+        if encode not in ("auto", "host", "device"):
+            raise ValueError(f"encode must be 'auto', 'host' or 'device', got {encode!r}")
+        self.encode = encode
         labels = []
         self.datasets = {}
         for d in datasets:
@@ -83,6 +94,9 @@ class SaveTrajectoryCallback:
 
         self._stager = dist.HostStager()  # one pinned + one device staging buffer for the whole run (dist.gather_ragged_to_host)
         self.gather_timings: Dict[str, float] = {}  # gather_s / gather_bytes accumulated over batches and labels (bench.py: e2e_sharded)
+        self._encoder = None  # traj_encode.DeviceTrajectoryEncoder, created with the first device-encoded batch
+        self._dev_blocks: dict = {}  # (label, first chain index) -> (device block [chains, n, T, 3], event recorded behind its producer)
+        self._joined_frames = {l: 0 for l in self.labels}  # models / frames in joined.pdb / joined.dcd
 
     def _dir(self, label: str, ext: str) -> str:
         d = os.path.join(self.output_dir, label, "predicted_samples", ext)
@@ -147,8 +161,36 @@ class SaveTrajectoryCallback:
         self._pending = still
         return error
 
+    def _use_device_encoder(self, sample: Sequence[dict]) -> bool:
+        if self.encode == "host":
+            return False
+        tensors = [s[self.sample_key] for s in sample if self.sample_key in s]
+        if not tensors:
+            return False  # (nothing to write)
+        on_gpu = all(torch.is_tensor(t) and t.is_cuda for t in tensors)
+        grouped = torch.distributed.is_available() and torch.distributed.is_initialized()
+        if self.encode == "device":
+            if not on_gpu:
+                raise RuntimeError("SaveTrajectoryCallback(encode='device') needs the sample tensors on a GPU; use encode='host' (or 'auto') for CPU tensors")
+            if grouped:
+                raise RuntimeError("SaveTrajectoryCallback(encode='device') does not run under a process group: the trajectory gather delivers host blocks")
+            from . import _lib
+
+            _lib.load()
+            return True
+        if not on_gpu or grouped:
+            return False
+        try:
+            from . import _lib
+
+            _lib.load()
+        except RuntimeError:
+            return False
+        return True
+
     def on_after_sample_batch(self, sample: Sequence[dict], sampler):
         error = self._finished_writer_error()
+        use_device = self._use_device_encoder(sample) and (self.write_dcd or self.write_pdb)
         for s in sample:
             if s.get("dataset_label") not in self.datasets:
                 raise KeyError(f"sample dataset label {s.get('dataset_label')!r} has no dataset")
@@ -168,17 +210,99 @@ class SaveTrajectoryCallback:
                 continue
             start = self.num_chains_seen[label]
             self.num_chains_seen[label] = start + sum(int(b.shape[0]) for b in blocks)
+            if use_device and block is not None and block.is_cuda and block.dtype == torch.float32 and block.shape[0] > 0 and block.shape[2] > 0:
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(block.device))
+                self._dev_blocks[(label, start)] = (block, ready)  # kept alive until the writer thread has encoded it
             self._submit(self._write_batch, label, blocks, start)
         if error is not None:  # (no label, so no gather to carry it)
             raise error
 
     def _write_batch(self, label: str, blocks: List[np.ndarray], start: int) -> None:
+        dev = self._dev_blocks.pop((label, start), None)
         new = [c for b in blocks for c in b]
         self.chains[label].extend(new)
+        if dev is not None:
+            self._write_batch_device(label, new, start, *dev)
+        else:
+            for i, arr in enumerate(new, start=start):
+                self._write_chain(label, i, arr, npy_index=(i - start) if self.npy_index_restarts_per_batch else None)
+            if self.chains[label]:
+                self._write_chain(label, "joined", np.concatenate(self.chains[label], axis=1))  # "b n t c -> n (b t) c"
+        self._joined_frames[label] = sum(int(c.shape[1]) for c in self.chains[label])
+
+    def _write_batch_device(self, label: str, new: List[np.ndarray], start: int, block: torch.Tensor, ready) -> None:
+        """The files of `_write_batch` with ``.pdb`` / ``.dcd`` bytes encoded on the GPU from ``block`` [chains, n, T, 3] (the device
+        twin of ``new``): per chain its own files, and ``joined.pdb`` / ``joined.dcd`` extended by the chain's frames (models
+        numbered on from the frames already there) instead of rewritten.  A file with a value the fixed PDB layout cannot hold
+        (counted by the kernel) is rewritten by `save_pdb`."""
+        from .pdb import append_dcd_frames, append_pdb_models, save_dcd, save_pdb
+        from .traj_encode import DeviceTrajectoryEncoder
+
         for i, arr in enumerate(new, start=start):
-            self._write_chain(label, i, arr, npy_index=(i - start) if self.npy_index_restarts_per_batch else None)
-        if self.chains[label]:
-            self._write_chain(label, "joined", np.concatenate(self.chains[label], axis=1))  # "b n t c -> n (b t) c"
+            np.save(self.filename_pred(label, (i - start) if self.npy_index_restarts_per_batch else i, "npy"), arr)
+        np.save(self.filename_pred(label, "joined", "npy"), np.concatenate(self.chains[label], axis=1))  # (axis 1: cannot be appended)
+        if self._encoder is None or self._encoder.device != block.device:
+            self._encoder = DeviceTrajectoryEncoder(block.device)
+        enc = self._encoder
+        enc.stream.wait_event(ready)
+        n, T = int(block.shape[1]), int(block.shape[2])
+        mol = self._mol(label) if self.write_pdb else None
+        tmpl = None
+        if mol is not None and len(mol["atom_names"]) == n and n + 1 <= 99999:
+            try:
+                tmpl = enc.template(mol)
+            except UnicodeEncodeError:
+                tmpl = None
+        pdb_chunk = enc.pdb_frames_per_chunk(int(tmpl[0].numel())) if tmpl is not None else 0
+        dcd_chunk = enc.dcd_frames_per_chunk(n) if self.write_dcd else 0
+        joined_pdb, joined_dcd = self.filename_pred(label, "joined", "pdb"), self.filename_pred(label, "joined", "dcd")
+        joined_at = self._joined_frames[label]
+        if joined_at == 0:  # files of an earlier run are replaced, as the host path does
+            for path in (joined_pdb, joined_dcd):
+                if os.path.exists(path):
+                    os.unlink(path)
+        host_frames = lambda arr: np.transpose(arr, (1, 0, 2))
+        joined_pdb_stale = False
+
+        def both(*sinks):
+            def sink(data):
+                for fn in sinks:
+                    fn(data)
+            return sink
+
+        for c, (i, arr) in enumerate(enumerate(new, start=start)):
+            frames = block[c].transpose(0, 1)  # [T, n, 3] view of the chain
+            own_pdb, own_dcd = self.filename_pred(label, i, "pdb"), self.filename_pred(label, i, "dcd")
+            for path in (own_pdb, own_dcd):
+                if os.path.exists(path):
+                    os.unlink(path)
+            jobs = []
+            if pdb_chunk > 0:
+                enc.reset_unencodable()
+                for t0 in range(0, T, pdb_chunk):
+                    t1 = min(T, t0 + pdb_chunk)
+                    jobs.append((enc.encode_pdb(frames[t0:t1], t0, *tmpl), lambda data, p=own_pdb: append_pdb_models(p, data)))
+                    jobs.append((enc.encode_pdb(frames[t0:t1], joined_at + t0, *tmpl), lambda data: append_pdb_models(joined_pdb, data)))
+            if dcd_chunk > 0:
+                for t0 in range(0, T, dcd_chunk):
+                    t1 = min(T, t0 + dcd_chunk)
+                    jobs.append((enc.encode_dcd(frames[t0:t1]), both(lambda data, p=own_dcd, k=t1 - t0: append_dcd_frames(p, n, data, k),
+                                                                     lambda data, k=t1 - t0: append_dcd_frames(joined_dcd, n, data, k))))
+            enc.run(jobs)
+            if pdb_chunk > 0 and enc.unencodable() != 0:
+                save_pdb(own_pdb, mol, host_frames(arr))
+                joined_pdb_stale = True
+            elif mol is not None and pdb_chunk == 0:  # (no template, or one model larger than the staging buffer: the host formatter)
+                save_pdb(own_pdb, mol, host_frames(arr))
+                joined_pdb_stale = True
+            if self.write_dcd and dcd_chunk == 0:
+                save_dcd(own_dcd, host_frames(arr))
+            joined_at += T
+        if joined_pdb_stale:
+            save_pdb(joined_pdb, mol, host_frames(np.concatenate(self.chains[label], axis=1)))
+        if self.write_dcd and dcd_chunk == 0:
+            save_dcd(joined_dcd, host_frames(np.concatenate(self.chains[label], axis=1)))
 
     def _submit(self, fn, *args) -> None:
         if not self.async_write:  # a failed synchronous write surfaces at the next batch too, through the same gather

@@ -1051,6 +1051,58 @@ int jamun_philox_normal(float* out_dev, int32_t n, uint64_t seed, uint32_t itera
   });
 }
 
+// ---- trajectory file encoders (jamun_traj.hip) ----------------------------------------------------------------------------------------
+
+namespace {
+constexpr int64_t kMaxModel = 1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
+
+int64_t checked_pdb_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames) {
+  if (body_len < 0 || first_model < 0 || n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+  if (body_len > INT32_MAX) throw Err(JAMUN_ERR_INVALID, "body_len must fit 31 bits");
+  if (first_model > kMaxModel || n_frames > kMaxModel) throw Err(JAMUN_ERR_INVALID, "model numbers must stay below 10^15");
+  return pdb_models_nbytes(body_len, first_model, n_frames);
+}
+}  // namespace
+
+int jamun_pdb_models_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames, int64_t* nbytes) {
+  return guarded([&] {
+    if (!nbytes) throw Err(JAMUN_ERR_INVALID, "null argument");
+    *nbytes = checked_pdb_nbytes(body_len, first_model, n_frames);
+  });
+}
+
+int jamun_encode_pdb_models(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, int64_t first_model,
+                            const uint8_t* body_dev, int64_t body_len, const int32_t* coord_off_dev, uint8_t* out_dev, int64_t out_capacity,
+                            uint32_t* unencodable_dev, void* stream) {
+  return guarded([&] {
+    if (!xyz_dev || !body_dev || !coord_off_dev || !out_dev || !unencodable_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (frame_stride < 0 || atom_stride < 0 || n_atoms < 0 || n_frames < 0 || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if ((int64_t)n_atoms + 1 > 99999) throw Err(JAMUN_ERR_INVALID, "n_atoms + 1 > 99999: the serial field of the ATOM / TER records would widen");
+    const int64_t need = checked_pdb_nbytes(body_len, first_model, n_frames);
+    if (out_capacity < need)
+      throw Err(JAMUN_ERR_INVALID, "out_capacity " + std::to_string(out_capacity) + " is too small: the models need " + std::to_string(need) + " bytes");
+    if (n_frames == 0) return;
+    launch_encode_pdb(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, first_model, body_dev, (int)body_len, coord_off_dev, out_dev,
+                      unencodable_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, uint8_t* out_dev,
+                            int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    if (!xyz_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (frame_stride < 0 || atom_stride < 0 || n_atoms < 0 || n_frames < 0 || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 3) throw Err(JAMUN_ERR_INVALID, "out_dev must be 4-byte aligned");
+    const int64_t need = (int64_t)n_frames * 3 * (4 * (int64_t)n_atoms + 8);
+    if (out_capacity < need)
+      throw Err(JAMUN_ERR_INVALID, "out_capacity " + std::to_string(out_capacity) + " is too small: the frames need " + std::to_string(need) + " bytes");
+    if (n_frames == 0) return;
+    launch_encode_dcd(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int jamun_build_edges(jamun_sampler* s, const float* y_dev, void* stream) {
   return guarded([&] {
     if (!s || !y_dev) throw Err(JAMUN_ERR_INVALID, "null argument");

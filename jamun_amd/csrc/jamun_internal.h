@@ -502,3 +502,8 @@ void launch_edge_geometry(const float* pos, const long long* src, const long lon
                           float* sh, float* radial, hipStream_t st);
 void launch_philox_normal(float* out, int n, uint64_t seed, uint32_t iter, uint32_t atom0, hipStream_t st);
 int launch_node_linear(const float* x, int n_atoms, int in0, int in1, int out0, int out1, const float* w, float* out, hipStream_t st);
+// jamun_traj.hip — trajectory file encoders (PDB model text, DCD coordinate records)
+long long pdb_models_nbytes(long long body_len, long long first_model, long long n_frames);
+void launch_encode_pdb(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, long long first_model,
+                       const unsigned char* body, int body_len, const int* coord_off, unsigned char* out, unsigned int* unencodable, hipStream_t st);
+void launch_encode_dcd(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, unsigned char* out, hipStream_t st);

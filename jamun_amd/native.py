@@ -454,3 +454,47 @@ def aboba_b(y, v, score, noise, params):
     lib = _lib.load()
     with torch.cuda.device(y.device):
         _lib.check(lib.jamun_aboba_b(_ptr(y), _ptr(v), _ptr(score), _ptr(noise), y.shape[0], C.byref(params), _stream()))
+
+
+# ---- trajectory file encoders (jamun_traj.hip) ---------------------------------------------------------------------------------------
+
+def pdb_models_nbytes(body_len: int, first_model: int, n_frames: int) -> int:
+    """Exact size of PDB models ``first_model .. first_model + n_frames - 1`` with a body of ``body_len`` bytes (host only)."""
+    lib = _lib.load()
+    out = C.c_int64()
+    _lib.check(lib.jamun_pdb_models_nbytes(int(body_len), int(first_model), int(n_frames), C.byref(out)))
+    return int(out.value)
+
+
+def _frame_strides(xyz: torch.Tensor) -> Tuple[int, int, int, int]:
+    """``xyz [T, n, 3]`` (any strides over T and n, components adjacent) -> (frame stride, atom stride, n, T) in floats: no copy."""
+    if not xyz.is_cuda or xyz.dtype != torch.float32 or xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise RuntimeError(f"frames must be a float32 [frames, atoms, 3] tensor on the GPU, got {xyz.dtype} {tuple(xyz.shape)} on {xyz.device}")
+    if xyz.shape[0] > 0 and xyz.shape[1] > 0 and xyz.stride(2) != 1:
+        raise RuntimeError("the three components of an atom must be adjacent in memory")
+    return int(xyz.stride(0)), int(xyz.stride(1)), int(xyz.shape[1]), int(xyz.shape[0])
+
+
+def encode_pdb_models(xyz: torch.Tensor, first_model: int, body: torch.Tensor, coord_off: torch.Tensor, out: torch.Tensor,
+                      unencodable: torch.Tensor) -> int:
+    """Queue the text of PDB models ``first_model ...`` of the frames ``xyz [T, n, 3]`` (device fp32, nm, a view of either trajectory
+    layout) into ``out`` (device uint8) on the current stream; returns the number of bytes.  ``body`` (uint8) / ``coord_off`` (int32)
+    are `pdb.pdb_model_template` on the device; ``unencodable`` (one int32, zeroed by the caller) counts the values the fixed
+    layout cannot hold.  See ``jamun_encode_pdb_models``."""
+    lib = _lib.load()
+    fs, as_, n, T = _frame_strides(xyz)
+    need = pdb_models_nbytes(body.numel(), first_model, T)
+    with torch.cuda.device(xyz.device):
+        _lib.check(lib.jamun_encode_pdb_models(_ptr(xyz), fs, as_, n, T, int(first_model), _ptr(body), int(body.numel()), _ptr(coord_off), _ptr(out),
+                                               int(out.numel()), _ptr(unencodable), _stream()))
+    return need
+
+
+def encode_dcd_frames(xyz: torch.Tensor, out: torch.Tensor) -> int:
+    """Queue the DCD coordinate records of the frames ``xyz [T, n, 3]`` into ``out`` (device uint8) on the current stream; returns the
+    number of bytes.  See ``jamun_encode_dcd_frames``."""
+    lib = _lib.load()
+    fs, as_, n, T = _frame_strides(xyz)
+    with torch.cuda.device(xyz.device):
+        _lib.check(lib.jamun_encode_dcd_frames(_ptr(xyz), fs, as_, n, T, _ptr(out), int(out.numel()), _stream()))
+    return T * 3 * (4 * n + 8)

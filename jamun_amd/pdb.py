@@ -209,6 +209,106 @@ def save_dcd(path: str, frames) -> None:
         f.write(recs.tobytes())
 
 
+def pdb_model_template(mol: dict):
+    """What `save_pdb` prints between ``MODEL <t>`` and the next model, once per molecule: ``(body, coord_offsets)`` — the bytes of
+    the ATOM records (coordinate fields blank), TER, the CONECT block and ``ENDMDL``, printed with the f-strings of `save_pdb`,
+    and per atom the byte offset of its x field in ``body`` (y and z follow, 8 characters each; ``int32[n]``, ascending).  Filling
+    the 3 x 8 characters per atom with ``f"{v:8.3f}"`` gives `save_pdb`'s model text byte for byte; the device encoder
+    (``jamun_encode_pdb_models``) does exactly that.  Raises ``UnicodeEncodeError`` for names outside ASCII (characters and bytes
+    would no longer coincide): such a molecule stays on `save_pdb`."""
+    import numpy as np
+
+    names, resn, els = mol["atom_names"], mol["residues"], mol["elements"]
+    n = len(names)
+    res_idx = [int(i) for i in mol["residue_sequence_index"]]
+    chain = [int(c) for c in mol.get("chain_index", [0] * n)]
+    partners = [[i + 1] for i in range(n)]
+    seen = set()
+    for a, b in mol["bonds"].T.tolist():
+        if (a, b) not in seen:
+            seen.add((a, b))
+            partners[a].append(b + 1)
+            partners[b].append(a + 1)
+    conect = "".join("CONECT" + "".join(f"{q:5d}" for q in ps) + "\n" for ps in partners)
+    parts: List[bytes] = []
+    offsets = np.empty(n, dtype=np.int32)
+    at = 0
+    for i in range(n):
+        head = f"ATOM  {i + 1:5d} {names[i]:<4s} {resn[i]:3s} {chain[i]:1d}{res_idx[i] + 1:4d}    ".encode("ascii")
+        tail = f"  1.00  0.00          {els[i]:>2s}\n".encode("ascii")
+        offsets[i] = at + len(head)
+        parts += [head, b" " * 24, tail]
+        at += len(head) + 24 + len(tail)
+    parts.append(f"TER   {n + 1:5d}      {resn[n - 1]:3s} {chain[n - 1]:1d}{res_idx[n - 1] + 1:4d}\n".encode("ascii"))
+    parts.append(conect.encode("ascii"))
+    parts.append(b"ENDMDL\n")
+    return b"".join(parts), offsets
+
+
+def append_pdb_models(path: str, data) -> None:
+    """Extend a multi-model PDB file by the model text ``data`` (bytes-like): the file is created, or its trailing ``END`` record is
+    dropped, then ``data`` and ``END`` follow — the result is `save_pdb` of all frames when ``data`` holds the models numbered on
+    from the ones already in the file."""
+    if os.path.exists(path):
+        with open(path, "r+b") as f:
+            size = f.seek(0, os.SEEK_END)
+            if size < 4:
+                raise ValueError(f"{path}: not a PDB file written by save_pdb (no END record)")
+            f.seek(size - 4)
+            if f.read(4) != b"END\n":
+                raise ValueError(f"{path}: does not end with an END record")
+            f.seek(size - 4)
+            f.truncate()
+            f.write(data)
+            f.write(b"END\n")
+    else:
+        with open(path, "wb") as f:
+            f.write(data)
+            f.write(b"END\n")
+
+
+def _dcd_preamble(nset: int, natom: int) -> bytes:
+    """The bytes of a `save_dcd` file in front of its coordinate records (header, title block, atom count)."""
+    import struct
+
+    icntrl = [0] * 20
+    icntrl[0], icntrl[1], icntrl[2], icntrl[3] = nset, 0, 1, nset  # NSET, ISTART, NSAVC, NSTEP
+    icntrl[19] = 24
+    head = b"CORD" + struct.pack("<9i", *icntrl[:9]) + struct.pack("<f", 1.0) + struct.pack("<10i", *icntrl[10:])
+    titles = [b"Created by jamun_amd (DCD, CHARMM format)".ljust(80), b"REMARKS coordinates in Angstrom".ljust(80)]
+    tb = struct.pack("<i", len(titles)) + b"".join(titles)
+    return (struct.pack("<i", 84) + head + struct.pack("<i", 84) + struct.pack("<i", len(tb)) + tb + struct.pack("<i", len(tb))
+            + struct.pack("<3i", 4, natom, 4))
+
+
+def append_dcd_frames(path: str, n_atoms: int, records, n_new: int) -> None:
+    """Extend a DCD file by ``n_new`` frames given as their coordinate records (bytes-like: per frame three Fortran records X, Y, Z,
+    the ``recs`` buffer of `save_dcd` / the output of ``jamun_encode_dcd_frames``).  A new file gets `save_dcd`'s header; an
+    existing one has its frame counts NSET (file offset 8) and NSTEP (file offset 20) raised by ``n_new``.  The result is `save_dcd`
+    of all frames."""
+    import struct
+
+    if len(memoryview(records).cast("B")) != n_new * 3 * (4 * n_atoms + 8):
+        raise ValueError(f"{n_new} frames of {n_atoms} atoms are {n_new * 3 * (4 * n_atoms + 8)} bytes of records, got {len(memoryview(records).cast('B'))}")
+    if not os.path.exists(path):
+        with open(path, "wb") as f:
+            f.write(_dcd_preamble(n_new, n_atoms))
+            f.write(records)
+        return
+    pre = _dcd_preamble(0, n_atoms)
+    with open(path, "r+b") as f:
+        have = f.read(len(pre))
+        if len(have) != len(pre) or have[:8] != pre[:8] or have[-12:] != pre[-12:]:
+            raise ValueError(f"{path}: not a DCD file of {n_atoms} atoms written by save_dcd")
+        nset = struct.unpack("<i", have[8:12])[0]
+        f.seek(8)
+        f.write(struct.pack("<i", nset + n_new))
+        f.seek(20)
+        f.write(struct.pack("<i", nset + n_new))
+        f.seek(0, os.SEEK_END)
+        f.write(records)
+
+
 class PDBDataset:
     """Single-structure dataset: what ``MDtrajDataset(root, trajfiles=[pdb], pdbfile=pdb, label)`` provides the sampler."""
 
