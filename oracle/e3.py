@@ -139,6 +139,17 @@ def wigner_3j(l1: int, l2: int, l3: int, dtype=torch.float32) -> torch.Tensor:
     return torch.tensor(_wigner_3j_np(l1, l2, l3), dtype=dtype)
 
 
+def _signed_w3j(l1: int, l2: int, l3: int, dtype, w3j_111_sign: float = 1.0) -> torch.Tensor:
+    """``wigner_3j`` under a checkpoint's sign convention for the one tensor whose sign is a convention of the real basis:
+    (1, 1, 1) = ``w3j_111_sign`` * epsilon / sqrt(6) (``jamun_hparams.w3j_111_sign``; +1 is e3nn 0.5.4 and leaves the tensor
+    untouched); every other tensor is as ``wigner_3j`` gives it."""
+    C = wigner_3j(l1, l2, l3, dtype=dtype)
+    if (l1, l2, l3) == (1, 1, 1) and float(w3j_111_sign) != 1.0:
+        assert float(w3j_111_sign) == -1.0, w3j_111_sign
+        C = -C
+    return C
+
+
 # ---------------------------------------------------------------------------
 # Spherical harmonics / radial basis  (call sites: src/jamun/model/arch/e3conv.py:41,116,119-126)
 # ---------------------------------------------------------------------------
@@ -249,8 +260,10 @@ def fctp(
     irreps_in1: Irreps,
     irreps_in2: Irreps,
     irreps_out: Irreps,
+    w3j_111_sign: float = 1.0,
 ) -> torch.Tensor:
-    """Per-sample-weight tensor product: ``weight`` is ``[batch, weight_numel]`` (materialised, as the reference)."""
+    """Per-sample-weight tensor product: ``weight`` is ``[batch, weight_numel]`` (materialised, as the reference).
+    ``w3j_111_sign``: sign convention of ``wigner_3j(1, 1, 1)`` (``_signed_w3j``)."""
     ins, numel = fctp_instructions(irreps_in1, irreps_in2, irreps_out)
     assert weight.shape[-1] == numel, (weight.shape, numel)
     s1, s2, so = irreps_slices(irreps_in1), irreps_slices(irreps_in2), irreps_slices(irreps_out)
@@ -263,7 +276,7 @@ def fctp(
         w = weight[:, off : off + m1 * m2 * mo].reshape(Z, m1, m2, mo)
         a = x1[:, s1[i1]].reshape(Z, m1, 2 * l1 + 1)
         b = x2[:, s2[i2]].reshape(Z, m2, 2 * l2 + 1)
-        C = wigner_3j(l1, l2, lo, dtype=x1.dtype)
+        C = _signed_w3j(l1, l2, lo, x1.dtype, w3j_111_sign)
         r = torch.einsum("zuvw,ijk,zui,zvj->zwk", w, C, a, b) * coef
         out[:, so[io]] += r.reshape(Z, mo * (2 * lo + 1))
     return out
@@ -297,7 +310,8 @@ def separable_weight_numel(irreps_in1: Irreps, irreps_in2: Irreps, irreps_out: I
     return separable_instructions(irreps_in1, irreps_in2, irreps_out)[2]
 
 
-def separable_tp(x1, x2, weight, lin_weight, irreps_in1: Irreps, irreps_in2: Irreps, irreps_out: Irreps) -> torch.Tensor:
+def separable_tp(x1, x2, weight, lin_weight, irreps_in1: Irreps, irreps_in2: Irreps, irreps_out: Irreps,
+                 w3j_111_sign: float = 1.0) -> torch.Tensor:
     """``SeparableTensorProduct.forward``: ``lin(dtp(x, y, weight))`` with per-sample ``weight [batch, weight_numel]`` for the
     depth-wise product and the shared flat ``lin_weight`` of the point-wise ``o3.Linear(irreps_out_dtp -> irreps_out)``."""
     ins, irreps_dtp, numel = separable_instructions(irreps_in1, irreps_in2, irreps_out)
@@ -311,7 +325,7 @@ def separable_tp(x1, x2, weight, lin_weight, irreps_in1: Irreps, irreps_in2: Irr
         w = weight[:, off : off + m1 * m2].reshape(Z, m1, m2)
         a = x1[:, s1[i]].reshape(Z, m1, 2 * l1 + 1)
         b = x2[:, s2[j]].reshape(Z, m2, 2 * l2 + 1)
-        C = wigner_3j(l1, l2, lo, dtype=x1.dtype)
+        C = _signed_w3j(l1, l2, lo, x1.dtype, w3j_111_sign)
         r = torch.einsum("zuv,ijk,zui,zvj->zuk", w, C, a, b) * coef
         mid[:, sd[k]] = r.reshape(Z, m1 * (2 * lo + 1))
     return linear(mid, lin_weight, irreps_dtp, irreps_out)
