@@ -370,6 +370,10 @@ int jamun_debug_plan_segments(int32_t cus, int32_t ng, int32_t n_k, int32_t n_at
  * (info only), else capacity >= info[0]. */
 int jamun_debug_segments(jamun_sampler* s, int32_t which, int32_t* out, int64_t capacity, int32_t* info);
 
+/* Device and pinned-host allocations the library holds in this process right now, over all samplers: their number and their bytes as
+ * requested (tests/test_gpu_memory.py: both return to their earlier values after a destroy and after a failed create).  Host only. */
+int jamun_debug_live_allocations(int64_t* count, int64_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

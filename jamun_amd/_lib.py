@@ -136,6 +136,7 @@ SYMBOLS = {
     "jamun_debug_plan_segments": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_double,
                                             _P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "jamun_debug_segments": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    "jamun_debug_live_allocations": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
 PROF_CLASSES = ["geom", "edge_h", "conv0_init", "conv1_init", "conv0", "conv1", "node_update", "head_finalize", "tprod"]

@@ -382,6 +382,340 @@ void check_mcmc(const jamun_mcmc_params* p) {
 
 bool saves(const jamun_mcmc_params* p, int i) { return (i % p->save_every_n_steps) == 0 && i >= p->burn_in_steps; }
 
+// ---- FLOP and byte model: what create fixes per sampler (count_flops) and what needs the edge count of the batch (fill_stats_model) ----
+void count_flops(jamun_sampler* s) {
+  const jamun_hparams& hp = s->hp;
+  for (auto& L : s->layers) {
+    s->flop_ref_per_edge += 2LL * hp.edge_attr_dim * hp.edge_attr_dim + 2LL * (hp.edge_attr_dim + 1) * L.tp_numel;  // SURVEY.md §8 d (SeparableConv: tp_numel = the 336 depth-wise weights)
+    if (s->conv_path == CONV_DG && &L != &s->layers[0]) {
+      // per (tile, k) in k_conv_dg: fp32 path 476 units of v_mfma_f32_32x32x2 (4096 FLOP); f16x3 path 150 v_mfma_f32_32x32x16_f16
+      // (32768 FLOP: 50 groups of 16 inputs x 3 products) + 72 v_mfma_f32_16x16x32_f16 (16384 FLOP); + 60 fp32 units per (32 atoms, k)
+      // in the T pre-pass
+      // (mode 4, jamun_conv_mf.hip: 414 v_mfma_f32_32x32x16_f16 per (tile, k): 228 forming + 186 contraction)
+      const int64_t per_tile_k = s->dg_mode == 5 ? (57LL * ((s->ml_window + 15) / 16) + 186) * 32768 : s->dg_mode == 4 ? (s->mf_nks == 3 ? 357LL : 414LL) * 32768 : s->dg_emu ? (150LL * 32768 + 72LL * 16384) : 476LL * 4096;
+      s->conv_flop_exec_launch = (int64_t)(s->dg_n_tiles - s->n_tail_tiles) * per_tile_k * (hp.edge_attr_dim + 1);  // (tail tiles run in their own kernels)
+      s->flop_exec += s->conv_flop_exec_launch + (int64_t)((s->n_atoms + 31) / 32) * (s->dg_emu ? 24LL * 32768 : 60LL * 4096) * (hp.edge_attr_dim + 1);
+    }
+    else if (L.sep.w2b) s->flop_exec += 3LL * 2 * (int64_t)s->n_atoms * 32 * ((s->S + 31) / 32) * 64 * 352;  // the per-edge weight GEMM as f16x3 (the rest is VALU work per edge)
+    else s->flop_exec += 2LL * s->n_pad * (1LL * L.p0.K * L.p0.nt * 32 + 3LL * L.p1.K * L.p1.nt * 32);
+  }
+}
+
+// e: edges of the current table; ml_cnt: k_conv_ml's own count of its MFMAs (mode 5 with launches so far; else unused)
+void fill_stats_model(const jamun_sampler* s, int64_t e, unsigned long long ml_cnt, jamun_stats* out) {
+  const int64_t m0 = s->hp.mul0, m1 = s->hp.mul1, H1 = s->hp.edge_attr_dim + 1, N = s->n_atoms;
+  const bool dg = s->conv_path == CONV_DG;
+  out->flop_ref_assoc = e * s->flop_ref_per_edge;
+  out->flop_executed = s->flop_exec;
+  out->conv0_flop_alg = 2 * N * H1 * (m0 + m1) * (m0 + m1);
+  out->conv1_flop_alg = 2 * 3 * N * H1 * (m0 + 2 * m1) * m1;
+  out->conv_flop_exec_launch = (s->x1 && s->dg_mode == 4) ? s->conv_flop_exec_launch / 3 : s->conv_flop_exec_launch;
+  if (dg && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0)  // (block-sparse forming: counted by the kernel; mean over its launches so far)
+    out->conv_flop_exec_launch = (int64_t)((double)ml_cnt / (double)s->ml_launches) * 32768;
+  if (dg && s->layers.size() > 1)  // one basis for both figures: the hidden layers' share of flop_executed follows the per-launch figure reported above (f16x1: a third; k_conv_ml: kernel-counted)
+    out->flop_executed += (int64_t)(s->layers.size() - 1) * (out->conv_flop_exec_launch - s->conv_flop_exec_launch);
+  out->conv_flop_useful_launch = out->conv_bytes_alg_launch = 0;
+  if (dg && s->layers.size() > 1) {
+    // (the launch these figures describe is the main conv kernel: destinations that go through the tail kernels are not its work — their
+    // edges are taken as the batch's mean in-degree, the slab and h~ bytes below stay whole: every slot is read, every slab row written)
+    const int64_t Nm = N - ((s->dg_mode == 4 && s->n_tail_tiles > 0) ? s->n_tail : 0), em = N > 0 ? (int64_t)((double)e * (double)Nm / (double)N) : 0;
+    const int64_t contraction = 2 * H1 * Nm * ((m0 + m1) * (m0 + m1) + 3 * m1 * (2 * m1));
+    // per edge and k: x0 (m0), dot 3 m1, x1 3 m1, cross 6 m1, T term 3 m1 — on the matrix cores only in k_conv_mf (k_conv_dg forms on the vector ALUs)
+    const int64_t forming = (s->dg_mode == 4 || s->dg_mode == 5) ? 2 * H1 * em * (m0 + 15 * m1) : 0;
+    out->conv_flop_useful_launch = (s->x1 ? 1 : s->dg_emu ? 3 : 1) * (contraction + forming);
+    const int64_t slots = (int64_t)s->h_kstride;
+    out->conv_bytes_alg_launch = 4 * (H1 * slots          // h~ of the layer
+                                      + H1 * 32 * N         // T
+                                      + N * s->XS           // feature rows
+                                      + (int64_t)s->dg_n_slabs * s->n_pad * 32 * (s->layers[1].p0.nt + 3 * s->layers[1].p1.nt)) +  // slabs
+                                 ((s->dg_mode == 4 || s->dg_mode == 5) ? H1 * 124 * 64 * 16 : s->dg_emu ? H1 * 4 * 34 * 64 * 16 : H1 * (5 * 16 + 5 * 4 + 2 * 4) * 64 * 16);  // weights
+  } else if (s->layers.size() > 1 && s->layers[1].sep.w2b) {
+    // SeparableConv hidden layer (k_sep_fused + k_sep_linear): h~ of the layer, one feature row per edge, the per-destination sums written
+    // and read once, the slab, W2~ and the Linear's weights once
+    const int64_t n0 = s->layers[1].sep.n0, n1 = s->layers[1].sep.n1, DW = n0 + n1 + 3 * (n0 + 2 * n1);
+    out->conv_bytes_alg_launch = 4 * (H1 * (int64_t)s->h_kstride + e * s->XS + 2 * N * DW + N * (160 + 96) +
+                                      (n0 + n1) * (m0 + m1) + (n0 + 2 * n1) * m1) + 4 * 11 * 2 * 1024;
+  }
+}
+
+// ---- sampler create, step by step (sampler_create_impl) ---------------------------------------------------------------------------
+struct TopoHost { std::vector<int> graph_of, bip, bis; int nmax = 0; };  // walker of every atom; bonded edges by destination (CSR: pointers, sources); atoms of the largest walker
+
+// validates ptr and the bond list, builds the bonded-edge CSR, sets the edge stride S
+TopoHost check_topology(jamun_sampler* s, const jamun_topology* topo) {
+  const int N = topo->n_atoms, W = topo->n_graphs;
+  TopoHost t;
+  for (int g = 0; g < W; ++g) {
+    if (topo->ptr[g + 1] < topo->ptr[g]) throw Err(JAMUN_ERR_INVALID, "ptr must be non-decreasing");
+    t.nmax = std::max(t.nmax, topo->ptr[g + 1] - topo->ptr[g]);
+  }
+  if (topo->ptr[0] != 0 || topo->ptr[W] != N) throw Err(JAMUN_ERR_INVALID, "ptr must span [0, n_atoms]");
+  t.graph_of.resize(N);
+  for (int g = 0; g < W; ++g)
+    for (int a = topo->ptr[g]; a < topo->ptr[g + 1]; ++a) t.graph_of[a] = g;
+  t.bip.assign(N + 1, 0);
+  t.bis.resize(topo->n_bonds);
+  for (int b = 0; b < topo->n_bonds; ++b) {
+    const int64_t sa = topo->bond_src[b], da = topo->bond_dst[b];
+    if (sa < 0 || sa >= N || da < 0 || da >= N) throw Err(JAMUN_ERR_INVALID, "bond index out of range");
+    if (t.graph_of[sa] != t.graph_of[da]) throw Err(JAMUN_ERR_INVALID, "bond connects two different walkers");
+    t.bip[da + 1]++;
+  }
+  int max_in = 0;
+  for (int i = 0; i < N; ++i) { max_in = std::max(max_in, t.bip[i + 1]); t.bip[i + 1] += t.bip[i]; }
+  std::vector<int> fill(t.bip.begin(), t.bip.end() - 1);
+  for (int b = 0; b < topo->n_bonds; ++b) t.bis[fill[topo->bond_dst[b]]++] = (int)topo->bond_src[b];  // stable: list order
+  s->S = std::min(std::max(t.nmax - 1, 0), JAMUN_MAX_NEIGHBORS + 1) + max_in;
+  if (s->S < 1) s->S = 1;
+  s->n_tiles = s->n_pad / 32;
+  return t;
+}
+
+void set_max_lds() {
+  const std::pair<const char*, int (*)()> lds_attr[] = {{"k_conv", conv_set_max_lds}, {"k_node_update", node_update_set_max_lds},
+                                                        {"k_conv_init_v", conv_initv_set_max_lds}, {"k_conv_dg", conv_dg_set_max_lds},
+                                                        {"k_tprod_t", tprod_set_max_lds}, {"jamun_conv_tail.hip", conv_tail_set_max_lds},
+                                                        {"jamun_conv_mf.hip", conv_mf_set_max_lds}, {"jamun_conv_ml.hip", conv_ml_set_max_lds},
+                                                        {"jamun_sepconv.hip", sep_conv_set_max_lds}, {"jamun_wide.hip", conv_wide_set_max_lds}};
+  for (auto& f : lds_attr)
+    if (f.second() != 0)
+      throw Err(JAMUN_ERR_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + f.first + ": " + hipGetErrorString(hipGetLastError()));
+}
+
+// radial basis centres: torch.linspace(0, r_cut, 34)[1:-1] in fp32 (e3nn soft_one_hot_linspace)
+void upload_radial_centres(jamun_sampler* s) {
+  const int nr = (s->hp.edge_attr_dim + 1) / 2, steps = nr + 2;
+  const float start = 0.f, end = s->r_cut;
+  const float step = (end - start) / (float)(steps - 1);
+  std::vector<float> vals(steps);
+  for (int i = 0; i < steps; ++i) vals[i] = (i < steps / 2) ? start + step * (float)i : end - step * (float)(steps - i - 1);
+  s->rb_step = vals[1] - vals[0];
+  std::vector<float> mu(vals.begin() + 1, vals.end() - 1);
+  s->mu = s->mem.upload(mu);
+}
+
+struct Embeddings { std::vector<float> xe_host, uniq; std::vector<int> uid; };  // the scaled embedding row of every atom; the distinct ones; [n_atoms] index into them
+
+// scaled atom embeddings (constant per topology and sigma): atom_embedding.py:58-76, noise_conditioning.py:50-54
+Embeddings upload_embeddings(jamun_sampler* s, const jamun_model* m, const jamun_topology* topo, double c_noise) {
+  const jamun_hparams& hp = s->hp;
+  const int N = s->n_atoms;
+  const char* names[4] = {"atom_embedder.atom_type_embedding.weight", "atom_embedder.atom_code_embedding.weight",
+                          "atom_embedder.residue_code_embedding.weight", "atom_embedder.residue_index_embedding.weight"};
+  const int32_t* idx[4] = {topo->atom_type_index, topo->atom_code_index, topo->residue_code_index, topo->residue_sequence_index};
+  std::vector<double> s0 = noise_mlp(*m, "initial_noise_scaling.scale_predictor", s->n_emb, c_noise);
+  Embeddings E;
+  std::vector<float>& xe = E.xe_host;
+  xe.assign((size_t)N * s->n_emb, 0.f);
+  int col = 0;
+  for (int tb = 0; tb < 4; ++tb) {
+    const auto& T = m->get(names[tb], (int64_t)hp.emb_rows[tb] * hp.emb_dim[tb]);
+    for (int i = 0; i < N; ++i) {
+      int row = idx[tb][i];
+      if (tb == 3 && !hp.use_residue_sequence_index) row = 0;
+      if (row < 0 || row >= hp.emb_rows[tb]) throw Err(JAMUN_ERR_INVALID, std::string("index out of range for ") + names[tb]);
+      for (int c = 0; c < hp.emb_dim[tb]; ++c)
+        xe[(size_t)i * s->n_emb + col + c] = (float)((double)T[(size_t)row * hp.emb_dim[tb] + c] * s0[col + c]);
+    }
+    col += hp.emb_dim[tb];
+  }
+  s->x_emb = s->mem.upload(xe);
+  // distinct rows of the scaled embedding (atoms with equal embedding indices share one): the initial projector's
+  // input-times-weight products are tabulated per distinct row
+  E.uid.resize(N);
+  std::map<std::vector<float>, int> seen;
+  for (int i = 0; i < N; ++i) {
+    std::vector<float> row(xe.begin() + (size_t)i * s->n_emb, xe.begin() + (size_t)(i + 1) * s->n_emb);
+    auto it = seen.find(row);
+    if (it == seen.end()) {
+      it = seen.emplace(row, (int)seen.size()).first;
+      E.uniq.insert(E.uniq.end(), row.begin(), row.end());
+    }
+    E.uid[i] = it->second;
+  }
+  return E;
+}
+
+void build_layers(jamun_sampler* s, const jamun_model* m, const Embeddings& E, double c_noise) {
+  const jamun_hparams& hp = s->hp;
+  const bool wide = s->conv_path == CONV_WIDE;
+  {
+    // initial projector: four scalar blocks (irreps not simplified, atom_embedding.py:54-56); scaling already in x_emb
+    std::vector<InBlock> ib;
+    int xo = 0;
+    const int muls[4] = {hp.emb_dim[0], hp.emb_dim[0], hp.emb_dim[2], hp.emb_dim[3]};
+    for (int b = 0; b < 4; ++b) { ib.push_back({muls[b], 0, xo, xo}); xo += muls[b]; }
+    std::vector<double> ones(s->n_emb, 1.0);
+    if (wide) s->layers.push_back(build_layer(s->mem, s->dg_mem, *m, "initial_projector", ib, ones, s->n_slices, nullptr, 0, false, nullptr, true));
+    else s->layers.push_back(build_layer(s->mem, s->dg_mem, *m, "initial_projector", ib, ones, s->n_slices, &E.uniq, s->n_emb, false, &E.xe_host));
+    s->n_uniq = (int)(E.uniq.size() / (size_t)std::max(s->n_emb, 1));
+    if (s->layers.back().tt2 || s->layers.back().tabw) s->atom_uid = s->mem.upload(E.uid);
+  }
+  for (int l = 0; l < hp.n_layers; ++l) {
+    std::vector<InBlock> ib = {{hp.mul0, 0, 0, 0}, {hp.mul1, 1, hp.mul0, hp.mul0}};
+    const std::string li = std::to_string(l);
+    std::vector<double> sc = noise_mlp(*m, "noise_scalings." + li + ".scale_predictor", hp.mul0 + hp.mul1, c_noise);
+    LayerDev L = build_layer(s->mem, s->dg_mem, *m, "layers." + li, ib, sc, s->n_slices, nullptr, 0, /*pack_dg=*/!s->tune.no_dg && !wide, nullptr, wide);
+    std::vector<double> wm = noise_mlp(*m, "skip_connections." + li + ".weights.scale_predictor", hp.mul0 + hp.mul1, c_noise);
+    std::vector<float> mix(wm.size());
+    for (size_t i = 0; i < wm.size(); ++i) mix[i] = (float)(1.0 / (1.0 + std::exp(-wm[i])));
+    L.mix = s->mem.upload(mix);
+    s->layers.push_back(L);
+  }
+  for (auto& L : s->layers)
+    if (L.sep.w2b)
+      if (const char* why = sep_conv_unsupported(L.sep.n0, L.sep.n1, L.p0.nt, L.p1.nt, s->S, hp.edge_attr_dim)) throw Err(JAMUN_ERR_INVALID, why);
+}
+
+// What select_kernels decided, into the sampler: its kernel choice always; for CONV_DG the tile plan, tail tiles and work lists
+void upload_plan(jamun_sampler* s, const KernelPlan& sel) {
+  DevArena& mem = s->mem;
+  s->conv_path = sel.conv_path;
+  s->init_path = sel.init_path;
+  s->dg_emu = sel.dg_emu;
+  if (sel.conv_path != CONV_DG) {  // the tile plan's weights are not needed: released now, not at destroy
+    s->dg_mem.clear();
+    for (auto& L : s->layers) L.dg = DgDev{};
+    return;
+  }
+  const int N = s->n_atoms, n_k = s->hp.edge_attr_dim + 1;
+  const TilePlan& T = sel.tiles;
+  s->dg_mode = sel.dg_mode; s->dg_row_blocks = T.row_blocks; s->dg_RS = sel.dg_RS; s->dg_n_tiles = (int)T.atoms.size();
+  s->ml_window = sel.ml_window; s->mf_nks = sel.mf_nks; s->initv_nbuf = sel.initv_nbuf; s->init_tail = sel.init_tail;
+  s->dg_grid = s->cus; s->dg_ng = sel.ng; s->dg_seg_cost_tenths = (int)std::lround(10 * sel.seg_cost);
+  if (!sel.tail_tiles.empty()) {
+    s->n_tail_tiles = (int)sel.tail_tiles.size(); s->n_tail = (int)sel.tail_atom.size(); s->tail_runs = sel.tail_runs;
+    s->tail_tiles = mem.upload(sel.tail_tiles);
+    s->tail_atom = mem.upload(sel.tail_atom);
+    s->tail_scale = mem.alloc<float>(sel.tail_atom.size());
+    s->tail_P = mem.alloc<float4>(sel.tail_P_bytes / 16);
+  }
+  // (round 6) every segment record carries its tile's descriptor — {k_extra, first destination, destinations | source rows << 8, first source row} —
+  // so that a kernel's first prologue is ONE round trip behind the segment list instead of two (list -> tile tables -> loads)
+  auto upload = [&](const SegPlan& P, int4*& segs_dev, int*& atom_nslab, int& max_segs, int& n_slabs) {
+    std::vector<int4> segs = P.segs;
+    for (size_t i = 0; i + 1 < segs.size(); i += 2) {
+      const int t = segs[i].x;
+      if (t < 0) continue;
+      segs[i + 1].y = T.atoms[t].x;
+      segs[i + 1].z = T.atoms[t].y | ((T.span[t].y - T.span[t].x) << 8);
+      segs[i + 1].w = T.span[t].x;
+    }
+    segs_dev = mem.upload(segs); atom_nslab = mem.upload(P.atom_nslab); max_segs = P.max_segs; n_slabs = P.n_slabs;
+  };
+  if (sel.own_init_segs) upload(sel.init_segs, s->init_segs, s->init_atom_nslab, s->init_max_segs, s->init_n_slabs);
+  upload(sel.segs, s->dg_segs, s->dg_atom_nslab, s->dg_max_segs, s->dg_n_slabs);
+  s->dg_tile_atoms = mem.upload(T.atoms);
+  s->dg_tile_span = mem.upload(T.span);
+  const bool mf = s->dg_mode == 4 || s->dg_mode == 5;
+  if (s->dg_mode == 5) s->ml_count = mem.zeroed<unsigned long long>(1);
+  if (mf) {
+    s->dg_tstride = ((N + 31) & ~31) + 64;
+    s->dg_T = mem.zeroed<float>((size_t)n_k * 32 * s->dg_tstride);
+    s->mf_err = mem.zeroed<int>(1);
+    s->mf_err_host = mem.pinned<int>(1);
+    *s->mf_err_host = 0;
+  } else {
+    s->dg_T = mem.alloc<float>((size_t)n_k * N * 32);
+  }
+  s->x1 = (s->tune.f16x1 && mf && s->dg_emu) ? 1 : 0;
+}
+
+void alloc_work_buffers(jamun_sampler* s) {
+  DevArena& mem = s->mem;
+  const jamun_hparams& hp = s->hp;
+  const bool wide = s->conv_path == CONV_WIDE;
+  const size_t N = (size_t)s->n_atoms, NS = N * s->S;
+  for (float** p : {&s->yc, &s->g, &s->tmp, &s->xhat_buf, &s->score_buf, &s->psi}) *p = mem.alloc<float>(N * 3);
+  s->deg = mem.alloc<int>(N);
+  s->esrc = mem.alloc<int>(NS);
+  s->epair = mem.zeroed<int>(NS);  // (pair table of the matrix-formed kernels, written by k_geom with the edges)
+  s->egeo = mem.alloc<float4>(NS);
+  std::vector<float> w1r_all, cmask_all;
+  for (auto& L : s->layers) {
+    w1r_all.insert(w1r_all.end(), L.w1r_h.begin(), L.w1r_h.end());
+    cmask_all.insert(cmask_all.end(), L.cmask_h.begin(), L.cmask_h.end());
+  }
+  s->w1r_all = mem.upload(w1r_all);
+  if (hp.edge_attr_dim == 64 && !s->tune.edge_h_fp32 && !wide) pack_edge_h16(s);
+  s->cmask_all = mem.upload(cmask_all);
+  s->h_kstride = (NS + 63) & ~(size_t)63;
+  s->h_stride = s->h_kstride * (wide ? (size_t)hp.edge_attr_dim + 1 : (size_t)JAMUN_HROWS);  // (H + 1 rows)
+  s->h_batched = s->h_stride * s->layers.size() * sizeof(float) <= ((size_t)4 << 30);  // all layers' h~ at once, up to 4 GiB
+  // (+ slack: k_conv_mf reads h~ at slot0 + p * stride without a bounds test; lanes past the last atom's slots read up to
+  // 32 * S + 128 floats beyond the table and never use them)
+  s->h = mem.alloc<float>(s->h_stride * (s->h_batched ? s->layers.size() : 1) + 32 * (size_t)s->S + 256);
+  int nt0 = 0, nt1 = 0;
+  for (auto& L : s->layers) { nt0 = std::max(nt0, L.p0.nt); nt1 = std::max(nt1, L.p1.nt); }
+  const size_t n_part = (size_t)std::max(std::max(s->n_slices, s->dg_n_slabs), s->init_n_slabs);
+  s->partial0 = mem.alloc<float>(n_part * s->n_pad * nt0 * 32);
+  s->partial1 = mem.alloc<float>(n_part * s->n_pad * 3 * nt1 * 32);
+  {
+    int dw = 0;
+    for (auto& L : s->layers)
+      if (L.sep.w2b) dw = std::max(dw, L.sep.n0 + L.sep.n1 + 3 * (L.sep.n0 + 2 * L.sep.n1));
+    if (dw > 0) s->sep_D = mem.alloc<float>(N * dw);
+  }
+  if (wide) {
+    int k0 = 8, k1 = 8;
+    for (auto& L : s->layers) { k0 = std::max(k0, L.K0w); k1 = std::max(k1, L.K1w); }
+    s->z0 = mem.zeroed<float>((size_t)s->n_pad * k0);
+    s->z1 = mem.zeroed<float>((size_t)3 * s->n_pad * k1);
+  }
+  for (size_t l = 0; l < s->layers.size(); ++l) s->x.push_back(mem.alloc<float>(N * s->XS));
+  s->counter = mem.alloc<unsigned long long>(1);
+}
+
+std::unique_ptr<jamun_sampler> sampler_create_impl(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning) {
+  jamun_tuning tn{};
+  if (tuning) tn = *tuning;
+  if (tn.dg_kgroups != 0 && tn.dg_kgroups != 1 && tn.dg_kgroups != 2 && tn.dg_kgroups != 4 && tn.dg_kgroups != 8)
+    throw Err(JAMUN_ERR_INVALID, "jamun_tuning.dg_kgroups must be 0 (default), 1, 2, 4 or 8");
+  if (tn.f16x1 != 0 && tn.f16x1 != 1) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.f16x1 must be 0 or 1");
+  if (tn.seg_cost_tenths < -1 || tn.seg_cost_tenths > 1000) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.seg_cost_tenths must be -1 (no segment cost), 0 (default) or 1..1000");
+  if (!(sigma > 0)) throw Err(JAMUN_ERR_INVALID, "sigma must be positive");
+  if (topo->n_atoms < 1 || topo->n_graphs < 1) throw Err(JAMUN_ERR_INVALID, "empty walker batch");
+  const jamun_hparams& hp = m->hp;
+  std::unique_ptr<jamun_sampler> s(new jamun_sampler());
+  s->hp = hp; s->tune = tn; s->sigma = sigma;
+  s->n_atoms = topo->n_atoms; s->n_graphs = topo->n_graphs;
+  s->n_pad = ((topo->n_atoms + 31) / 32) * 32;
+  s->XS = hp.mul0 + 3 * hp.mul1;
+  s->n_emb = hp.emb_dim[0] + hp.emb_dim[1] + hp.emb_dim[2] + hp.emb_dim[3];
+  s->conv_path = base_conv_path(hp, s->n_emb);
+  // ---- normalisation factors in fp32, op for op as Denoiser.normalization_factors (denoiser.py:116-136,177-178)
+  {
+    const float A = hp.average_squared_distance;
+    const float B = 6.0f * (sigma * sigma);
+    s->c_in = 1.0f / sqrtf(A + B);
+    s->c_skip = A / (A + B);
+    s->c_out = sqrtf((A * B) / (A + B));
+    const float mr2 = (float)((double)hp.max_radius * (double)hp.max_radius);
+    s->r_cut = sqrtf(mr2 + 6.0f * (sigma * sigma)) / s->c_in;
+    s->r2 = s->r_cut * s->r_cut;
+  }
+  const double c_noise = std::log((double)sigma) / 4.0;
+  const TopoHost th = check_topology(s.get(), topo);
+  set_max_lds();
+  s->ptr = s->mem.upload(std::vector<int>(topo->ptr, topo->ptr + topo->n_graphs + 1));
+  s->bond_in_ptr = s->mem.upload(th.bip);
+  s->bond_in_src = s->mem.upload(th.bis);
+  upload_radial_centres(s.get());
+  const Embeddings E = upload_embeddings(s.get(), m, topo, c_noise);
+  build_layers(s.get(), m, E, c_noise);
+  pack_head(*m, s.get());
+  int dev = 0, cus = 0;
+  HIPCHECK(hipGetDevice(&dev));
+  HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  s->cus = std::max(cus, 1);
+  // ---- kernel selection (jamun_plan.cpp); upload of the tile plan and work lists of the destination-grouped kernels
+  upload_plan(s.get(), select_kernels(hp, tn, *topo, th.graph_of, th.nmax, s->S, s->cus, s->conv_path, s->layers, s->n_uniq, s->atom_uid != nullptr));
+  alloc_work_buffers(s.get());
+  count_flops(s.get());
+  HIPCHECK(hipDeviceSynchronize());
+  return s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -402,364 +736,27 @@ int jamun_model_create(const jamun_hparams* hp, const jamun_tensor* tensors, int
     if (hp->mul1 == 0) throw Err(JAMUN_ERR_INVALID, "irreps_hidden needs at least one 1e channel (output is 1x1e)");
     if (hp->emb_dim[0] != hp->emb_dim[1])
       throw Err(JAMUN_ERR_INVALID, "atom_type and atom_code embedding dims must match (reference atom_embedding.py:54-56)");
-    auto* m = new jamun_model();
+    std::unique_ptr<jamun_model> m(new jamun_model());
     m->hp = *hp;
     for (int i = 0; i < n_tensors; ++i) {
-      if (!tensors[i].name || (!tensors[i].data && tensors[i].numel > 0)) {
-        delete m;
-        throw Err(JAMUN_ERR_INVALID, "tensor table entry with null name/data");
-      }
+      if (!tensors[i].name || (!tensors[i].data && tensors[i].numel > 0)) throw Err(JAMUN_ERR_INVALID, "tensor table entry with null name/data");
       m->t[tensors[i].name] = std::vector<float>(tensors[i].data, tensors[i].data + tensors[i].numel);
     }
-    *out = m;
+    *out = m.release();
   });
 }
 void jamun_model_destroy(jamun_model* m) { delete m; }
 
-static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning, jamun_sampler** out);
 static void sampler_self_check(const jamun_model* m, float sigma, const jamun_topology* topo, jamun_sampler* s);
 
 int jamun_sampler_create(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning, jamun_sampler** out) {
   return guarded([&] {
     if (!m || !topo || !out) throw Err(JAMUN_ERR_INVALID, "null argument");
     if (tuning && (tuning->selfcheck < -1 || tuning->selfcheck > 2)) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.selfcheck must be -1 (off), 0 (default: on), 1 (on) or 2 (on, with an injected fault)");
-    jamun_sampler* s = nullptr;
-    sampler_create_impl(m, sigma, topo, tuning, &s);
-    std::unique_ptr<jamun_sampler> hold(s);
-    if (!tuning || tuning->selfcheck >= 0) sampler_self_check(m, sigma, topo, s);
-    *out = hold.release();
-  });
-}
-
-static void sampler_create_impl(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning, jamun_sampler** out) {
-  {
-    jamun_tuning tn{};
-    if (tuning) tn = *tuning;
-    if (tn.dg_kgroups != 0 && tn.dg_kgroups != 1 && tn.dg_kgroups != 2 && tn.dg_kgroups != 4 && tn.dg_kgroups != 8)
-      throw Err(JAMUN_ERR_INVALID, "jamun_tuning.dg_kgroups must be 0 (default), 1, 2, 4 or 8");
-    if (tn.f16x1 != 0 && tn.f16x1 != 1) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.f16x1 must be 0 or 1");
-    if (tn.seg_cost_tenths < -1 || tn.seg_cost_tenths > 1000) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.seg_cost_tenths must be -1 (no segment cost), 0 (default) or 1..1000");
-    if (!(sigma > 0)) throw Err(JAMUN_ERR_INVALID, "sigma must be positive");
-    if (topo->n_atoms < 1 || topo->n_graphs < 1) throw Err(JAMUN_ERR_INVALID, "empty walker batch");
-    const jamun_hparams& hp = m->hp;
-    std::unique_ptr<jamun_sampler> s(new jamun_sampler());
-    s->hp = hp;
-    s->tune = tn;
-    s->sigma = sigma;
-    s->n_atoms = topo->n_atoms;
-    s->n_graphs = topo->n_graphs;
-    s->n_pad = ((topo->n_atoms + 31) / 32) * 32;
-    s->XS = hp.mul0 + 3 * hp.mul1;
-    s->n_emb = hp.emb_dim[0] + hp.emb_dim[1] + hp.emb_dim[2] + hp.emb_dim[3];
-    s->conv_path = base_conv_path(hp, s->n_emb);
-    const bool wide = s->conv_path == CONV_WIDE;
-    const int N = topo->n_atoms, W = topo->n_graphs;
-    // ---- normalisation factors in fp32, op for op as Denoiser.normalization_factors (denoiser.py:116-136,177-178)
-    {
-      const float A = hp.average_squared_distance;
-      const float B = 6.0f * (sigma * sigma);
-      s->c_in = 1.0f / sqrtf(A + B);
-      s->c_skip = A / (A + B);
-      s->c_out = sqrtf((A * B) / (A + B));
-      const float mr2 = (float)((double)hp.max_radius * (double)hp.max_radius);
-      s->r_cut = sqrtf(mr2 + 6.0f * (sigma * sigma)) / s->c_in;
-      s->r2 = s->r_cut * s->r_cut;
-    }
-    const double c_noise = std::log((double)sigma) / 4.0;
-    // ---- graph structure
-    int nmax = 0;
-    for (int g = 0; g < W; ++g) {
-      if (topo->ptr[g + 1] < topo->ptr[g]) throw Err(JAMUN_ERR_INVALID, "ptr must be non-decreasing");
-      nmax = std::max(nmax, topo->ptr[g + 1] - topo->ptr[g]);
-    }
-    if (topo->ptr[0] != 0 || topo->ptr[W] != N) throw Err(JAMUN_ERR_INVALID, "ptr must span [0, n_atoms]");
-    std::vector<int> graph_of(N);
-    for (int g = 0; g < W; ++g)
-      for (int a = topo->ptr[g]; a < topo->ptr[g + 1]; ++a) graph_of[a] = g;
-    std::vector<int> bip(N + 1, 0), bis(topo->n_bonds);
-    for (int b = 0; b < topo->n_bonds; ++b) {
-      const int64_t sa = topo->bond_src[b], da = topo->bond_dst[b];
-      if (sa < 0 || sa >= N || da < 0 || da >= N) throw Err(JAMUN_ERR_INVALID, "bond index out of range");
-      if (graph_of[sa] != graph_of[da]) throw Err(JAMUN_ERR_INVALID, "bond connects two different walkers");
-      bip[da + 1]++;
-    }
-    int max_in = 0;
-    for (int i = 0; i < N; ++i) { max_in = std::max(max_in, bip[i + 1]); bip[i + 1] += bip[i]; }
-    {
-      std::vector<int> fill(bip.begin(), bip.end() - 1);
-      for (int b = 0; b < topo->n_bonds; ++b) bis[fill[topo->bond_dst[b]]++] = (int)topo->bond_src[b];  // stable: list order
-    }
-    s->S = std::min(std::max(nmax - 1, 0), JAMUN_MAX_NEIGHBORS + 1) + max_in;
-    if (s->S < 1) s->S = 1;
-    s->n_tiles = s->n_pad / 32;
-    {
-      const std::pair<const char*, int (*)()> lds_attr[] = {{"k_conv", conv_set_max_lds}, {"k_node_update", node_update_set_max_lds},
-                                                            {"k_conv_init_v", conv_initv_set_max_lds}, {"k_conv_dg", conv_dg_set_max_lds},
-                                                            {"k_tprod_t", tprod_set_max_lds}, {"jamun_conv_tail.hip", conv_tail_set_max_lds},
-                                                            {"jamun_conv_mf.hip", conv_mf_set_max_lds}, {"jamun_conv_ml.hip", conv_ml_set_max_lds},
-                                                            {"jamun_sepconv.hip", sep_conv_set_max_lds}, {"jamun_wide.hip", conv_wide_set_max_lds}};
-      for (auto& f : lds_attr)
-        if (f.second() != 0)
-          throw Err(JAMUN_ERR_HIP, std::string("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed for ") + f.first + ": " + hipGetErrorString(hipGetLastError()));
-    }
-    std::vector<int> ptr_h(topo->ptr, topo->ptr + W + 1);
-    s->ptr = dev_upload(ptr_h);
-    s->bond_in_ptr = dev_upload(bip);
-    s->bond_in_src = dev_upload(bis);
-    // ---- radial basis centres: torch.linspace(0, r_cut, 34)[1:-1] in fp32 (e3nn soft_one_hot_linspace)
-    {
-      const int nr = (hp.edge_attr_dim + 1) / 2, steps = nr + 2;
-      const float start = 0.f, end = s->r_cut;
-      const float step = (end - start) / (float)(steps - 1);
-      std::vector<float> vals(steps);
-      for (int i = 0; i < steps; ++i) vals[i] = (i < steps / 2) ? start + step * (float)i : end - step * (float)(steps - i - 1);
-      s->rb_step = vals[1] - vals[0];
-      std::vector<float> mu(vals.begin() + 1, vals.end() - 1);
-      s->mu = dev_upload(mu);
-    }
-    // ---- scaled atom embeddings (constant per topology and sigma): atom_embedding.py:58-76, noise_conditioning.py:50-54
-    std::vector<float> xe_host;
-    {
-      const char* names[4] = {"atom_embedder.atom_type_embedding.weight", "atom_embedder.atom_code_embedding.weight",
-                              "atom_embedder.residue_code_embedding.weight", "atom_embedder.residue_index_embedding.weight"};
-      const int32_t* idx[4] = {topo->atom_type_index, topo->atom_code_index, topo->residue_code_index,
-                               topo->residue_sequence_index};
-      std::vector<double> s0 = noise_mlp(*m, "initial_noise_scaling.scale_predictor", s->n_emb, c_noise);
-      std::vector<float>& xe = xe_host;
-      xe.assign((size_t)N * s->n_emb, 0.f);
-      int col = 0;
-      for (int tb = 0; tb < 4; ++tb) {
-        const auto& T = m->get(names[tb], (int64_t)hp.emb_rows[tb] * hp.emb_dim[tb]);
-        for (int i = 0; i < N; ++i) {
-          int row = idx[tb][i];
-          if (tb == 3 && !hp.use_residue_sequence_index) row = 0;
-          if (row < 0 || row >= hp.emb_rows[tb]) throw Err(JAMUN_ERR_INVALID, std::string("index out of range for ") + names[tb]);
-          for (int c = 0; c < hp.emb_dim[tb]; ++c)
-            xe[(size_t)i * s->n_emb + col + c] = (float)((double)T[(size_t)row * hp.emb_dim[tb] + c] * s0[col + c]);
-        }
-        col += hp.emb_dim[tb];
-      }
-      s->x_emb = dev_upload(xe);
-    }
-    // ---- layers
-    {
-      // initial projector: four scalar blocks (irreps not simplified, atom_embedding.py:54-56); scaling already in x_emb
-      std::vector<InBlock> ib;
-      int xo = 0;
-      const int muls[4] = {hp.emb_dim[0], hp.emb_dim[0], hp.emb_dim[2], hp.emb_dim[3]};
-      for (int b = 0; b < 4; ++b) { ib.push_back({muls[b], 0, xo, xo}); xo += muls[b]; }
-      std::vector<double> ones(s->n_emb, 1.0);
-      // distinct rows of the scaled embedding (atoms with equal embedding indices share one): the initial projector's
-      // input-times-weight products are tabulated per distinct row
-      std::vector<float> uniq;
-      std::vector<int> uid(N);
-      {
-        std::map<std::vector<float>, int> seen;
-        for (int i = 0; i < N; ++i) {
-          std::vector<float> row(xe_host.begin() + (size_t)i * s->n_emb, xe_host.begin() + (size_t)(i + 1) * s->n_emb);
-          auto it = seen.find(row);
-          if (it == seen.end()) {
-            it = seen.emplace(row, (int)seen.size()).first;
-            uniq.insert(uniq.end(), row.begin(), row.end());
-          }
-          uid[i] = it->second;
-        }
-      }
-      if (wide) s->layers.push_back(build_layer(*m, "initial_projector", ib, ones, s->n_slices, nullptr, 0, false, nullptr, true));
-      else s->layers.push_back(build_layer(*m, "initial_projector", ib, ones, s->n_slices, &uniq, s->n_emb, false, &xe_host));
-      s->n_uniq = (int)(uniq.size() / (size_t)std::max(s->n_emb, 1));
-      if (s->layers.back().tt2 || s->layers.back().tabw) s->atom_uid = dev_upload(uid);
-    }
-    for (int l = 0; l < hp.n_layers; ++l) {
-      std::vector<InBlock> ib = {{hp.mul0, 0, 0, 0}, {hp.mul1, 1, hp.mul0, hp.mul0}};
-      const std::string li = std::to_string(l);
-      std::vector<double> sc = noise_mlp(*m, "noise_scalings." + li + ".scale_predictor", hp.mul0 + hp.mul1, c_noise);
-      LayerDev L = build_layer(*m, "layers." + li, ib, sc, s->n_slices, nullptr, 0, /*pack_dg=*/!tn.no_dg && !wide, nullptr, wide);
-      std::vector<double> wm = noise_mlp(*m, "skip_connections." + li + ".weights.scale_predictor", hp.mul0 + hp.mul1, c_noise);
-      std::vector<float> mix(wm.size());
-      for (size_t i = 0; i < wm.size(); ++i) mix[i] = (float)(1.0 / (1.0 + std::exp(-wm[i])));
-      L.mix = dev_upload(mix);
-      s->layers.push_back(L);
-    }
-    for (auto& L : s->layers)
-      if (L.sep.w2b)
-        if (const char* why = sep_conv_unsupported(L.sep.n0, L.sep.n1, L.p0.nt, L.p1.nt, s->S, hp.edge_attr_dim)) throw Err(JAMUN_ERR_INVALID, why);
-    // ---- head (EquivariantMLP, _mlp.py:84-114) and output gain (e3conv.py:134-135)
-    {
-      const int mul0 = hp.mul0, mul1 = hp.mul1, G0 = mul0 + mul1;
-      const auto& Wl = m->get("output_head.0.lin.weight", (int64_t)mul0 * G0 + (int64_t)mul1 * mul1);
-      const auto& Wo = m->get("output_head.1.weight", mul1);
-      const auto& gain = m->get("output_gain", 1);
-      std::vector<float> wg((size_t)mul0 * mul1), wv((size_t)mul1 * mul1), wo(mul1);
-      for (int u = 0; u < mul0; ++u)
-        for (int w = 0; w < mul1; ++w) wg[(size_t)u * mul1 + w] = (float)((double)Wl[(size_t)u * G0 + mul0 + w] / std::sqrt((double)mul0));
-      for (int i = 0; i < mul1 * mul1; ++i) wv[i] = (float)((double)Wl[(size_t)mul0 * G0 + i] / std::sqrt((double)mul1));
-      for (int w = 0; w < mul1; ++w) wo[w] = (float)((double)Wo[w] / std::sqrt((double)mul1) * (double)gain[0]);
-      s->w_gate = dev_upload(wg);
-      s->w_vec = dev_upload(wv);
-      s->w_out = dev_upload(wo);
-    }
-    hipDeviceProp_t prop;
-    {
-      int dev = 0;
-      HIPCHECK(hipGetDevice(&dev));
-      HIPCHECK(hipGetDeviceProperties(&prop, dev));
-    }
-    const int cus = std::max(prop.multiProcessorCount, 1);
-    s->cus = cus;
-    const int n_k = hp.edge_attr_dim + 1;
-    // ---- kernel selection (jamun_plan.cpp); upload of the tile plan and work lists of the destination-grouped kernels
-    const KernelPlan sel = select_kernels(hp, tn, *topo, graph_of, nmax, s->S, cus, s->conv_path, s->layers, s->n_uniq, s->atom_uid != nullptr);
-    s->conv_path = sel.conv_path;
-    s->init_path = sel.init_path;
-    s->dg_emu = sel.dg_emu;
-    if (sel.conv_path == CONV_DG) {
-      const TilePlan& T = sel.tiles;
-      s->dg_mode = sel.dg_mode; s->dg_row_blocks = T.row_blocks; s->dg_RS = sel.dg_RS; s->dg_n_tiles = (int)T.atoms.size();
-      s->ml_window = sel.ml_window; s->mf_nks = sel.mf_nks; s->initv_nbuf = sel.initv_nbuf; s->init_tail = sel.init_tail;
-      s->dg_grid = cus; s->dg_ng = sel.ng; s->dg_seg_cost_tenths = (int)std::lround(10 * sel.seg_cost);
-      if (!sel.tail_tiles.empty()) {
-        s->n_tail_tiles = (int)sel.tail_tiles.size(); s->n_tail = (int)sel.tail_atom.size(); s->tail_runs = sel.tail_runs;
-        s->tail_tiles = dev_upload(sel.tail_tiles);
-        s->tail_atom = dev_upload(sel.tail_atom);
-        s->tail_scale = dev_alloc<float>(sel.tail_atom.size());
-        s->tail_P = dev_alloc<float4>(sel.tail_P_bytes / 16);
-      }
-      // (round 6) every segment record carries its tile's descriptor — {k_extra, first destination, destinations | source rows << 8, first source row} —
-      // so that a kernel's first prologue is ONE round trip behind the segment list instead of two (list -> tile tables -> loads)
-      auto embed = [&](std::vector<int4> segs) {
-        for (size_t i = 0; i + 1 < segs.size(); i += 2) {
-          const int t = segs[i].x;
-          if (t < 0) continue;
-          segs[i + 1].y = T.atoms[t].x;
-          segs[i + 1].z = T.atoms[t].y | ((T.span[t].y - T.span[t].x) << 8);
-          segs[i + 1].w = T.span[t].x;
-        }
-        return dev_upload(segs);
-      };
-      auto upload = [&](const SegPlan& P, int4*& segs, int*& atom_nslab, int& max_segs, int& n_slabs) {
-        segs = embed(P.segs); atom_nslab = dev_upload(P.atom_nslab); max_segs = P.max_segs; n_slabs = P.n_slabs;
-      };
-      if (sel.own_init_segs) upload(sel.init_segs, s->init_segs, s->init_atom_nslab, s->init_max_segs, s->init_n_slabs);
-      upload(sel.segs, s->dg_segs, s->dg_atom_nslab, s->dg_max_segs, s->dg_n_slabs);
-      s->dg_tile_atoms = dev_upload(T.atoms);
-      s->dg_tile_span = dev_upload(T.span);
-      if (s->dg_mode == 5) {
-        s->ml_count = dev_alloc<unsigned long long>(1);
-        HIPCHECK(hipMemset(s->ml_count, 0, sizeof(unsigned long long)));
-      }
-      if (s->dg_mode == 4 || s->dg_mode == 5) {
-        s->dg_tstride = ((N + 31) & ~31) + 64;
-        s->dg_T = dev_alloc<float>((size_t)n_k * 32 * s->dg_tstride);
-        HIPCHECK(hipMemset(s->dg_T, 0, sizeof(float) * (size_t)n_k * 32 * s->dg_tstride));
-        s->mf_err = dev_alloc<int>(1);
-        HIPCHECK(hipMemset(s->mf_err, 0, sizeof(int)));
-        HIPCHECK(hipHostMalloc((void**)&s->mf_err_host, sizeof(int), hipHostMallocDefault));
-        *s->mf_err_host = 0;
-      } else {
-        s->dg_T = dev_alloc<float>((size_t)n_k * N * 32);
-      }
-      s->x1 = (tn.f16x1 && (s->dg_mode == 4 || s->dg_mode == 5) && s->dg_emu) ? 1 : 0;
-    } else {
-      for (auto& L : s->layers) free_dg(L.dg);
-    }
-    // ---- work buffers
-    const size_t NS = (size_t)N * s->S;
-    s->yc = dev_alloc<float>((size_t)N * 3);
-    s->deg = dev_alloc<int>(N);
-    s->esrc = dev_alloc<int>(NS);
-    s->epair = dev_alloc<int>(NS);  // (pair table of the matrix-formed kernels, written by k_geom with the edges)
-    HIPCHECK(hipMemset(s->epair, 0, sizeof(int) * NS));
-    s->egeo = dev_alloc<float4>(NS);
-    {
-      std::vector<float> w1r_all, cmask_all;
-      for (auto& L : s->layers) {
-        w1r_all.insert(w1r_all.end(), L.w1r_h.begin(), L.w1r_h.end());
-        cmask_all.insert(cmask_all.end(), L.cmask_h.begin(), L.cmask_h.end());
-      }
-      s->w1r_all = dev_upload(w1r_all);
-      if (hp.edge_attr_dim == 64 && !tn.edge_h_fp32 && !wide) {
-        // f16x3 radial MLP (k_edge_h16): W1's radial part per layer scaled to the top of the f16 range and split hi + lo, as A fragments
-        std::vector<float4> w1h;
-        std::vector<float> isc;
-        for (auto& L : s->layers) {
-          double wmax = 0;
-          for (float v : L.w1r_h) wmax = std::max(wmax, (double)std::fabs(v));
-          int ex = 0;
-          if (wmax > 0 && std::isfinite(wmax)) std::frexp(wmax, &ex);
-          const int sW = std::max(-40, std::min(40, 14 - ex));
-          isc.push_back((float)std::ldexp(1.0, -14 - sW));
-          const double sc = std::ldexp(1.0, sW);
-          for (int mt = 0; mt < 2; ++mt)
-            for (int s2 = 0; s2 < 2; ++s2) {
-              std::vector<float4> hi(64), lo(64);
-              for (int lane = 0; lane < 64; ++lane) {
-                const int hh = lane >> 5, k = 32 * mt + (lane & 31);
-                double v[8];
-                for (int j = 0; j < 8; ++j) v[j] = (double)L.w1r_h[(size_t)(16 * s2 + 8 * hh + j) * 64 + k] * sc;  // w1r: [basis][hidden]
-                pack8(v, hi[lane], lo[lane]);
-              }
-              w1h.insert(w1h.end(), hi.begin(), hi.end());
-              w1h.insert(w1h.end(), lo.begin(), lo.end());
-            }
-        }
-        s->w1h_all = dev_upload(w1h);
-        s->w1isc_all = dev_upload(isc);
-      }
-      s->cmask_all = dev_upload(cmask_all);
-      s->h_kstride = (NS + 63) & ~(size_t)63;
-      s->h_stride = s->h_kstride * (wide ? (size_t)hp.edge_attr_dim + 1 : (size_t)JAMUN_HROWS);  // (H + 1 rows)
-      s->h_batched = s->h_stride * s->layers.size() * sizeof(float) <= ((size_t)4 << 30);  // all layers' h~ at once, up to 4 GiB
-      // (+ slack: k_conv_mf reads h~ at slot0 + p * stride without a bounds test; lanes past the last atom's slots read up to
-      // 32 * S + 128 floats beyond the table and never use them)
-      s->h = dev_alloc<float>(s->h_stride * (s->h_batched ? s->layers.size() : 1) + 32 * (size_t)s->S + 256);
-    }
-    int nt0 = 0, nt1 = 0;
-    for (auto& L : s->layers) { nt0 = std::max(nt0, L.p0.nt); nt1 = std::max(nt1, L.p1.nt); }
-    const size_t n_part = (size_t)std::max(std::max(s->n_slices, s->dg_n_slabs), s->init_n_slabs);
-    s->partial0 = dev_alloc<float>(n_part * s->n_pad * nt0 * 32);
-    s->partial1 = dev_alloc<float>(n_part * s->n_pad * 3 * nt1 * 32);
-    {
-      int dw = 0;
-      for (auto& L : s->layers)
-        if (L.sep.w2b) dw = std::max(dw, L.sep.n0 + L.sep.n1 + 3 * (L.sep.n0 + 2 * L.sep.n1));
-      if (dw > 0) s->sep_D = dev_alloc<float>((size_t)N * dw);
-    }
-    if (wide) {
-      int k0 = 8, k1 = 8;
-      for (auto& L : s->layers) { k0 = std::max(k0, L.K0w); k1 = std::max(k1, L.K1w); }
-      s->z0 = dev_alloc<float>((size_t)s->n_pad * k0);
-      s->z1 = dev_alloc<float>((size_t)3 * s->n_pad * k1);
-      HIPCHECK(hipMemset(s->z0, 0, sizeof(float) * (size_t)s->n_pad * k0));
-      HIPCHECK(hipMemset(s->z1, 0, sizeof(float) * (size_t)3 * s->n_pad * k1));
-    }
-    s->g = dev_alloc<float>((size_t)N * 3);
-    s->tmp = dev_alloc<float>((size_t)N * 3);
-    s->xhat_buf = dev_alloc<float>((size_t)N * 3);
-    s->score_buf = dev_alloc<float>((size_t)N * 3);
-    s->psi = dev_alloc<float>((size_t)N * 3);
-    for (size_t l = 0; l < s->layers.size(); ++l) s->x.push_back(dev_alloc<float>((size_t)N * s->XS));
-    s->counter = dev_alloc<unsigned long long>(1);
-    // ---- FLOP bookkeeping
-    s->flop_ref_per_edge = 0;
-    s->flop_exec = 0;
-    for (auto& L : s->layers) {
-      s->flop_ref_per_edge += 2LL * hp.edge_attr_dim * hp.edge_attr_dim + 2LL * (hp.edge_attr_dim + 1) * L.tp_numel;  // SURVEY.md §8 d (SeparableConv: tp_numel = the 336 depth-wise weights)
-      if (s->conv_path == CONV_DG && &L != &s->layers[0]) {
-        // per (tile, k) in k_conv_dg: fp32 path 476 units of v_mfma_f32_32x32x2 (4096 FLOP); f16x3 path 150 v_mfma_f32_32x32x16_f16
-        // (32768 FLOP: 50 groups of 16 inputs x 3 products) + 72 v_mfma_f32_16x16x32_f16 (16384 FLOP); + 60 fp32 units per (32 atoms, k)
-        // in the T pre-pass
-        // (mode 4, jamun_conv_mf.hip: 414 v_mfma_f32_32x32x16_f16 per (tile, k): 228 forming + 186 contraction)
-        const int64_t per_tile_k = s->dg_mode == 5 ? (57LL * ((s->ml_window + 15) / 16) + 186) * 32768 : s->dg_mode == 4 ? (s->mf_nks == 3 ? 357LL : 414LL) * 32768 : s->dg_emu ? (150LL * 32768 + 72LL * 16384) : 476LL * 4096;
-        s->conv_flop_exec_launch = (int64_t)(s->dg_n_tiles - s->n_tail_tiles) * per_tile_k * (hp.edge_attr_dim + 1);  // (tail tiles run in their own kernels)
-        s->flop_exec += s->conv_flop_exec_launch + (int64_t)((s->n_atoms + 31) / 32) * (s->dg_emu ? 24LL * 32768 : 60LL * 4096) * (hp.edge_attr_dim + 1);
-      }
-      else if (L.sep.w2b) s->flop_exec += 3LL * 2 * (int64_t)N * 32 * ((s->S + 31) / 32) * 64 * 352;  // the per-edge weight GEMM as f16x3 (the rest is VALU work per edge)
-      else s->flop_exec += 2LL * s->n_pad * (1LL * L.p0.K * L.p0.nt * 32 + 3LL * L.p1.K * L.p1.nt * 32);
-    }
-    HIPCHECK(hipDeviceSynchronize());
+    std::unique_ptr<jamun_sampler> s = sampler_create_impl(m, sigma, topo, tuning);
+    if (!tuning || tuning->selfcheck >= 0) sampler_self_check(m, sigma, topo, s.get());
     *out = s.release();
-  }
+  });
 }
 
 // Create-time self-check: a build whose specialised kernels compute something else than the general ones must not sample.
@@ -777,9 +774,7 @@ static void sampler_self_check(const jamun_model* m, float sigma, const jamun_to
   rt.no_dg = rt.no_mf = rt.no_mfi = rt.no_init_v = rt.no_ml = rt.no_tail = 1;
   rt.node_fp32 = rt.edge_h_fp32 = 1;
   rt.selfcheck = -1;
-  jamun_sampler* rp = nullptr;
-  sampler_create_impl(m, sigma, topo, &rt, &rp);
-  std::unique_ptr<jamun_sampler> r(rp);
+  const std::unique_ptr<jamun_sampler> r = sampler_create_impl(m, sigma, topo, &rt);
   const int N = s->n_atoms;
   std::vector<float> y((size_t)N * 3);
   {
@@ -796,8 +791,8 @@ static void sampler_self_check(const jamun_model* m, float sigma, const jamun_to
       }
     }
   }
-  float* y_dev = dev_upload(y);
-  struct Free { float* p; ~Free() { hipFree(p); } } free_y{y_dev};
+  DevArena y_mem;
+  float* y_dev = y_mem.upload(y);
   if (s->tune.selfcheck == 2 && s->layers.size() > 1) {
     // fault injection (tests): 4 KB of the first hidden layer's weight stream of the SELECTED kernel read as zeros from here on
     float4* w = s->layers[1].dg.wm ? s->layers[1].dg.wm : s->layers[1].dg.wxh ? s->layers[1].dg.wxh : s->layers[1].dg.wx;
@@ -1147,60 +1142,24 @@ int jamun_sampler_stats(jamun_sampler* s, jamun_stats* out, void* stream) {
       if (s->mf_err_host) *s->mf_err_host = mf_flag;
       mf_err_check(s);
     }
+    const bool dg = s->conv_path == CONV_DG;
+    unsigned long long ml_cnt = 0;
+    if (dg && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0) HIPCHECK(hipMemcpy(&ml_cnt, s->ml_count, sizeof(ml_cnt), hipMemcpyDeviceToHost));
+    fill_stats_model(s, (int64_t)e, ml_cnt, out);
     out->n_edges = (int64_t)e;
-    out->flop_ref_assoc = (int64_t)e * s->flop_ref_per_edge;
-    out->flop_executed = s->flop_exec;
     out->conv_k0 = s->layers.back().p0.K;
     out->conv_k1 = s->layers.back().p1.K;
-    {
-      const int64_t m0 = s->hp.mul0, m1 = s->hp.mul1, H1 = s->hp.edge_attr_dim + 1;
-      out->conv0_flop_alg = 2 * (int64_t)s->n_atoms * H1 * (m0 + m1) * (m0 + m1);
-      out->conv1_flop_alg = 2 * 3 * (int64_t)s->n_atoms * H1 * (m0 + 2 * m1) * m1;
-    }
     out->edge_stride = s->S;
-    const bool dg = s->conv_path == CONV_DG;
     out->n_slices = dg ? s->dg_n_slabs : s->n_slices;
     out->conv_path = std::max(0, (int)s->conv_path);  // (SeparableConv: reported as 0, like the general kernels)
     out->dg_mode = dg ? s->dg_mode : -1;
     out->init_path = std::max(0, (int)s->init_path);
     out->dg_row_blocks = dg && s->dg_row_blocks ? 1 : 0;
     out->dg_emu = s->conv_path == CONV_WIDE ? 0 : dg ? (s->x1 ? 2 : s->dg_emu) : -1;  // (the wide path: fp32 MFMAs, jamun_tuning.f16x1 ignored)
-    out->conv_flop_exec_launch = (s->x1 && s->dg_mode == 4) ? s->conv_flop_exec_launch / 3 : s->conv_flop_exec_launch;
-    if (dg && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0) {  // (block-sparse forming: counted by the kernel; mean over its launches so far)
-      unsigned long long cnt = 0;
-      HIPCHECK(hipMemcpy(&cnt, s->ml_count, sizeof(cnt), hipMemcpyDeviceToHost));
-      out->conv_flop_exec_launch = (int64_t)((double)cnt / (double)s->ml_launches) * 32768;
-    }
-    if (dg && s->layers.size() > 1)  // one basis for both figures: the hidden layers' share of flop_executed follows the per-launch figure reported above (f16x1: a third; k_conv_ml: kernel-counted)
-      out->flop_executed += (int64_t)(s->layers.size() - 1) * (out->conv_flop_exec_launch - s->conv_flop_exec_launch);
     out->n_tail_tiles = s->n_tail_tiles;
     out->n_tail = s->n_tail;
     out->mf_nks = (dg && s->dg_mode == 4) ? s->mf_nks : 0;
     out->ml_window = (dg && s->dg_mode == 5) ? s->ml_window : 0;
-    out->conv_flop_useful_launch = 0;
-    out->conv_bytes_alg_launch = 0;
-    if (dg && s->layers.size() > 1) {
-      const int64_t m0 = s->hp.mul0, m1 = s->hp.mul1, H1 = s->hp.edge_attr_dim + 1, N = s->n_atoms;
-      // (the launch these figures describe is the main conv kernel: destinations that go through the tail kernels are not its work — their
-      // edges are taken as the batch's mean in-degree, the slab and h~ bytes below stay whole: every slot is read, every slab row written)
-      const int64_t Nm = N - ((s->dg_mode == 4 && s->n_tail_tiles > 0) ? s->n_tail : 0), em = N > 0 ? (int64_t)((double)e * (double)Nm / (double)N) : 0;
-      const int64_t contraction = 2 * H1 * Nm * ((m0 + m1) * (m0 + m1) + 3 * m1 * (2 * m1));
-      // per edge and k: x0 (m0), dot 3 m1, x1 3 m1, cross 6 m1, T term 3 m1 — on the matrix cores only in k_conv_mf (k_conv_dg forms on the vector ALUs)
-      const int64_t forming = (s->dg_mode == 4 || s->dg_mode == 5) ? 2 * H1 * em * (m0 + 15 * m1) : 0;
-      out->conv_flop_useful_launch = (s->x1 ? 1 : s->dg_emu ? 3 : 1) * (contraction + forming);
-      const int64_t slots = (int64_t)s->h_kstride;
-      out->conv_bytes_alg_launch = 4 * (H1 * slots          // h~ of the layer
-                                        + H1 * 32 * N         // T
-                                        + N * s->XS           // feature rows
-                                        + (int64_t)s->dg_n_slabs * s->n_pad * 32 * (s->layers[1].p0.nt + 3 * s->layers[1].p1.nt)) +  // slabs
-                                   ((s->dg_mode == 4 || s->dg_mode == 5) ? H1 * 124 * 64 * 16 : s->dg_emu ? H1 * 4 * 34 * 64 * 16 : H1 * (5 * 16 + 5 * 4 + 2 * 4) * 64 * 16);  // weights
-    } else if (s->layers.size() > 1 && s->layers[1].sep.w2b) {
-      // SeparableConv hidden layer (k_sep_fused + k_sep_linear): h~ of the layer, one feature row per edge, the per-destination sums written
-      // and read once, the slab, W2~ and the Linear's weights once
-      const int64_t n0 = s->layers[1].sep.n0, n1 = s->layers[1].sep.n1, DW = n0 + n1 + 3 * (n0 + 2 * n1), N = s->n_atoms;
-      out->conv_bytes_alg_launch = 4 * ((int64_t)(s->hp.edge_attr_dim + 1) * (int64_t)s->h_kstride + (int64_t)e * s->XS + 2 * N * DW + N * (160 + 96) +
-                                        (n0 + n1) * (int64_t)(s->hp.mul0 + s->hp.mul1) + (n0 + 2 * n1) * (int64_t)s->hp.mul1) + 4 * 11 * 2 * 1024;
-    }
   });
 }
 
@@ -1258,6 +1217,13 @@ int jamun_debug_stamps(unsigned long long* out8) {
     conv_ml_print_stamps();
     node_print_stamps();
     for (int i = 0; i < 8; ++i) out8[i] = 0;
+  });
+}
+
+int jamun_debug_live_allocations(int64_t* count, int64_t* bytes) {
+  return guarded([&] {
+    if (!count || !bytes) throw Err(JAMUN_ERR_INVALID, "null argument");
+    *count = DevArena::live_allocs; *bytes = DevArena::live_bytes;
   });
 }
 

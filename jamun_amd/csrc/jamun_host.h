@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <map>
 #include <stdexcept>
@@ -24,18 +25,43 @@ struct Err : std::runtime_error {
     if (_e != hipSuccess) throw Err(JAMUN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
 
-template <typename T>
-T* dev_alloc(size_t n) {
-  T* p = nullptr;
-  HIPCHECK(hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)));
-  return p;
-}
-template <typename T>
-T* dev_upload(const std::vector<T>& v) {
-  T* p = dev_alloc<T>(v.size());
-  if (!v.empty()) HIPCHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return p;
-}
+// Owner of device (and pinned host) memory: every allocation it hands out is recorded and freed by clear() / the destructor, so a throw
+// anywhere in sampler create gives back what was uploaded so far.  Structs keep plain T* fields into it.  live_allocs / live_bytes count
+// what all arenas of the process hold (jamun_debug_live_allocations).
+class DevArena {
+  struct Block { void* p; size_t bytes; bool pinned; };
+  std::vector<Block> blocks_;
+  void* take(size_t bytes, bool pinned) {
+    blocks_.reserve(blocks_.size() + 1);  // (so that recording the block cannot throw once it exists)
+    void* p = nullptr;
+    HIPCHECK(pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes));
+    blocks_.push_back({p, bytes, pinned});
+    ++live_allocs; live_bytes += (int64_t)bytes;
+    return p;
+  }
+
+ public:
+  static inline std::atomic<int64_t> live_allocs{0}, live_bytes{0};
+  DevArena() = default;
+  DevArena(const DevArena&) = delete;
+  DevArena& operator=(const DevArena&) = delete;
+  ~DevArena() { clear(); }
+  template <typename T> T* alloc(size_t n) { return (T*)take(std::max<size_t>(n, 1) * sizeof(T), false); }
+  template <typename T> T* pinned(size_t n) { return (T*)take(std::max<size_t>(n, 1) * sizeof(T), true); }
+  template <typename T> T* zeroed(size_t n) { T* p = alloc<T>(n); HIPCHECK(hipMemset(p, 0, std::max<size_t>(n, 1) * sizeof(T))); return p; }
+  template <typename T> T* upload(const std::vector<T>& v) {
+    T* p = alloc<T>(v.size());
+    if (!v.empty()) HIPCHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return p;
+  }
+  void clear() {
+    for (const Block& b : blocks_) {
+      b.pinned ? hipHostFree(b.p) : hipFree(b.p);
+      --live_allocs; live_bytes -= (int64_t)b.bytes;
+    }
+    blocks_.clear();
+  }
+};
 
 struct jamun_model {
   jamun_hparams hp;
@@ -105,12 +131,10 @@ struct LayerDev {
 };
 
 // ---- jamun_pack.cpp -----------------------------------------------------------------------------
-void free_dg(DgDev& d);
-void free_problem(ConvProblemDev& p);
-void pack8(const double (&v)[8], float4& hi, float4& lo);  // eight values, split into f16 hi + lo: one lane's fragment of an f16 MFMA in each plane
 std::vector<double> noise_mlp(const jamun_model& m, const std::string& prefix, int k, double c_noise);
 struct InBlock { int mul, l, xoff, ch0; };
-LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
+// (mem owns the layer's buffers; dg_mem those of L.dg, the tile plan's weights, which create releases early when the plan is not selected)
+LayerDev build_layer(DevArena& mem, DevArena& dg_mem, const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
                      const std::vector<double>& s_in, int n_slices,
                      const std::vector<float>* uniq_rows = nullptr, int row_len = 0, bool pack_dg = false,
                      const std::vector<float>* all_rows = nullptr, bool wide = false);
@@ -134,6 +158,7 @@ enum InitPath {
 };
 
 struct jamun_sampler {
+  DevArena mem, dg_mem;  // every device buffer below (dg_mem: LayerDev::dg); declared first: freed last, after the event pool
   jamun_hparams hp;
   jamun_tuning tune{};  // kernel-selection switches of jamun_sampler_create (all zero: defaults)
   float sigma = 0;
@@ -206,27 +231,11 @@ struct jamun_sampler {
   std::vector<std::pair<int, std::pair<int, int>>> ev_used;  // (class, (begin, end))
   size_t ev_next = 0;
 
-  ~jamun_sampler() {
-    hipFree(ptr); hipFree(bond_in_ptr); hipFree(bond_in_src); hipFree(x_emb); hipFree(mu);
-    hipFree(atom_uid); hipFree(w1r_all); hipFree(cmask_all); hipFree(w1h_all); hipFree(w1isc_all);
-    hipFree(epair); hipFree(dg_tile_atoms); hipFree(dg_tile_span); hipFree(dg_segs); hipFree(dg_atom_nslab); hipFree(dg_T); hipFree(mf_err); hipFree(ml_count);
-    hipFree(tail_tiles); hipFree(tail_atom); hipFree(tail_scale); hipFree(tail_P); hipFree(init_segs); hipFree(init_atom_nslab);
-    if (mf_err_host) hipHostFree(mf_err_host);
-    for (auto& L : layers) {
-      free_problem(L.p0); free_problem(L.p1); free_dg(L.dg);
-      hipFree(L.sep.w2b); hipFree(L.sep.cfw); hipFree(L.sep.bias); hipFree(L.sep.wl0); hipFree(L.sep.wl1);
-      hipFree(L.wcat0); hipFree(L.wcat1); hipFree(L.wh0); hipFree(L.wh1); hipFree(L.kga0); hipFree(L.kga1); hipFree(L.kgx); hipFree(L.cg0); hipFree(L.cg1); hipFree(L.mix); hipFree(L.tt2); hipFree(L.tabw);
-      hipFree(L.wx); hipFree(L.xph); hipFree(L.xpl); hipFree(L.xcf0); hipFree(L.xcf1); hipFree(L.wn0); hipFree(L.wn1);
-    }
-    hipFree(z0); hipFree(z1);
-    hipFree(w_gate); hipFree(w_vec); hipFree(w_out);
-    hipFree(yc); hipFree(h); hipFree(partial0); hipFree(partial1); hipFree(g); hipFree(tmp);
-    hipFree(xhat_buf); hipFree(score_buf); hipFree(psi); hipFree(deg); hipFree(esrc); hipFree(egeo);
-    for (float* p : x) hipFree(p);
-    hipFree(counter); hipFree(sep_D);
-    for (hipEvent_t e : ev_pool) hipEventDestroy(e);
-  }
+  ~jamun_sampler() { for (hipEvent_t e : ev_pool) hipEventDestroy(e); }
 };
+
+void pack_head(const jamun_model& m, jamun_sampler* s);  // w_gate / w_vec / w_out
+void pack_edge_h16(jamun_sampler* s);                    // w1h_all / w1isc_all from the layers' w1r_h
 
 // ---- jamun_plan.cpp -----------------------------------------------------------------------------
 void plan_tiles(const int32_t* ptr, const std::vector<int>& graph_of, int N, int cap, std::vector<int2>& t_atoms,

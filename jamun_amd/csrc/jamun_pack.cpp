@@ -5,16 +5,6 @@
 
 #include "jamun_host.h"
 
-void free_dg(DgDev& d) {
-  hipFree(d.wx); hipFree(d.wd); hipFree(d.wv); hipFree(d.wt); hipFree(d.wxh); hipFree(d.wth); hipFree(d.wm);
-  hipFree(d.gx); hipFree(d.gT); hipFree(d.cf0); hipFree(d.cf1); hipFree(d.cfT); hipFree(d.wmt); hipFree(d.cf1t);
-  d = DgDev{};
-}
-
-void free_problem(ConvProblemDev& p) {
-  hipFree(p.wpack); hipFree(p.chunks); hipFree(p.slice_ptr); hipFree(p.ublk); hipFree(p.lane_xoff);
-}
-
 namespace {
 
 // ---- packed conv problem ------------------------------------------------------------------------
@@ -76,8 +66,8 @@ int pow2_above(double v) { int ex = 0; if (v > 0 && std::isfinite(v)) std::frexp
 
 }  // namespace
 
-// eight values -> one lane's B fragment of an f16 MFMA, hi and lo planes
-void pack8(const double (&v)[8], float4& hi, float4& lo) {
+// eight values -> one lane's fragment of an f16 MFMA, hi and lo planes
+static void pack8(const double (&v)[8], float4& hi, float4& lo) {
   uint32_t h[4], l[4];
   for (int i = 0; i < 4; ++i) {
     uint16_t h0, l0, h1, l1;
@@ -140,7 +130,7 @@ std::vector<std::pair<int, int>> k_subgroups(int n_k, int n_slices, int ksub, st
 }
 
 // (wide = true: the chunking of k_conv_wide — k-subgroups of 1..ksub, an even number of weight groups per chunk)
-ConvProblemDev pack_problem(const std::vector<UBlock>& blocks, int planes, int G, int n_slices, int ksub,
+ConvProblemDev pack_problem(DevArena& mem, const std::vector<UBlock>& blocks, int planes, int G, int n_slices, int ksub,
                             const std::vector<float>& W3, const std::vector<float>& b3, int hidden, bool wide = false) {
   ConvProblemDev P;
   P.planes = planes;
@@ -208,11 +198,7 @@ ConvProblemDev pack_problem(const std::vector<UBlock>& blocks, int planes, int G
     }
   }
   P.xw = xw;
-  P.wpack = dev_upload(wp);
-  P.chunks = dev_upload(chunks);
-  P.slice_ptr = dev_upload(sp);
-  P.ublk = dev_upload(ub);
-  P.lane_xoff = dev_upload(lx);
+  P.wpack = mem.upload(wp); P.chunks = mem.upload(chunks); P.slice_ptr = mem.upload(sp); P.ublk = mem.upload(ub); P.lane_xoff = mem.upload(lx);
   return P;
 }
 
@@ -220,7 +206,7 @@ void pad_even(UBlock& b) {
   if (b.e.size() % 2) b.e.push_back(UEntry{b.type, 0, 0, 0, 0.0});
 }
 
-void build_layer_common(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks, const std::vector<double>& s_in,
+void build_layer_common(DevArena& mem, const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks, const std::vector<double>& s_in,
                         LayerDev& L, int in0, int in1, bool wide = false) {
   const jamun_hparams& hp = m.hp;
   const int mul0 = hp.mul0, mul1 = hp.mul1, H = hp.edge_attr_dim;
@@ -319,12 +305,12 @@ void build_layer_common(const jamun_model& m, const std::string& prefix, const s
           }
       return out;
     };
-    L.wn0 = dev_upload(pack_wide(wf0, mul0, ws0, in0, mul0, L.K0w));
-    L.wn1 = dev_upload(pack_wide(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1w));
+    L.wn0 = mem.upload(pack_wide(wf0, mul0, ws0, in0, mul0, L.K0w));
+    L.wn1 = mem.upload(pack_wide(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1w));
     return;  // (the compiled-width node-update kernels are not used on the wide path)
   }
-  L.wcat0 = dev_upload(pack_cat(wf0, mul0, ws0, in0, mul0, L.K0p));
-  L.wcat1 = dev_upload(pack_cat(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1p));
+  L.wcat0 = mem.upload(pack_cat(wf0, mul0, ws0, in0, mul0, L.K0p));
+  L.wcat1 = mem.upload(pack_cat(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1p));
   // f16x3 node update: the same matrices balanced by exact powers of two — row K (an input channel) times 2^-e_K so that its largest
   // magnitude sits in [0.5, 1), then column w times 2^sW_w so that its largest sits in [2^13, 2^14) — and split hi + lo; K padded to 16.
   // rowf[K] = 2^e_K multiplies the input when the kernel stages it, colf[w] = 2^-sW_w the output column.
@@ -373,8 +359,8 @@ void build_layer_common(const jamun_model& m, const std::string& prefix, const s
   };
   {
     std::vector<float> r0, c0, r1, c1;
-    L.wh0 = dev_upload(pack_cat_h(wf0, mul0, ws0, in0, mul0, L.K0h, r0, c0));
-    L.wh1 = dev_upload(pack_cat_h(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1h, r1, c1));
+    L.wh0 = mem.upload(pack_cat_h(wf0, mul0, ws0, in0, mul0, L.K0h, r0, c0));
+    L.wh1 = mem.upload(pack_cat_h(wf1, mul1, ws1, in1, std::max(mul1, 1), L.K1h, r1, c1));
     // row factors in the layouts the kernel reads them: activated scalars [mul0], gated vectors [mul1], and the channels of x_in in
     // x_in's own layout (in0 scalars, then in1 vectors x 3 components)
     std::vector<float> ka0(r0.begin(), r0.begin() + mul0), ka1(std::max(mul1, 1), 1.f), kx((size_t)((in0 + 3 * in1 + 3) & ~3), 1.f);
@@ -383,7 +369,7 @@ void build_layer_common(const jamun_model& m, const std::string& prefix, const s
     for (int u = 0; u < in1; ++u)
       for (int mm = 0; mm < 3; ++mm) kx[in0 + 3 * u + mm] = r1[mul1 + u];
     ka0.resize((size_t)((mul0 + 3) & ~3) + 4, 1.f);
-    L.kga0 = dev_upload(ka0); L.kga1 = dev_upload(ka1); L.kgx = dev_upload(kx); L.cg0 = dev_upload(c0); L.cg1 = dev_upload(c1);
+    L.kga0 = mem.upload(ka0); L.kga1 = mem.upload(ka1); L.kgx = mem.upload(kx); L.cg0 = mem.upload(c0); L.cg1 = mem.upload(c1);
   }
 }
 
@@ -391,7 +377,7 @@ void build_layer_common(const jamun_model& m, const std::string& prefix, const s
 // input block, for sh in (0e, 1e), for l_out = |l1 - l2| .. l1 + l2 kept when it occurs in the output irreps or is 0e — each with
 // mul_in weights and its own block of irreps_out_dtp; then o3.Linear(irreps_out_dtp -> G0 x0e + G1 x1e).  Packed in the canonical
 // order of jamun_sepconv.hip: weights [A | B | C | D | E], Linear rows scalars [D0 | D3], vectors [D1 | D2 | D4].
-LayerDev build_layer_separable(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks, const std::vector<double>& s_in,
+LayerDev build_layer_separable(DevArena& mem, const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks, const std::vector<double>& s_in,
                                LayerDev& L) {
   const jamun_hparams& hp = m.hp;
   const int mul0 = hp.mul0, mul1 = hp.mul1, G0 = mul0 + mul1, G1 = mul1, H = hp.edge_attr_dim;
@@ -494,18 +480,14 @@ LayerDev build_layer_separable(const jamun_model& m, const std::string& prefix, 
       const double nrm = 1.0 / std::sqrt((double)(scalar_out ? K0 : K1));
       for (int w = 0; w < G; ++w) (scalar_out ? wl0 : wl1)[(size_t)row * G + w] = (float)((double)WL[t.loff + (int64_t)u * G + w] * nrm);
     }
-  L.sep.w2b = dev_upload(w2b);
-  L.sep.cfw = dev_upload(cfw);
-  L.sep.bias = dev_upload(bias);
-  L.sep.wl0 = dev_upload(wl0);
-  L.sep.wl1 = dev_upload(wl1);
+  L.sep.w2b = mem.upload(w2b); L.sep.cfw = mem.upload(cfw); L.sep.bias = mem.upload(bias); L.sep.wl0 = mem.upload(wl0); L.sep.wl1 = mem.upload(wl1);
   L.sep.n0 = n0; L.sep.n1 = n1;
   L.p0.nt = (G0 + 31) / 32;  // (the node update reads the slab widths from here)
   L.p1.nt = (G1 + 31) / 32;
   L.p0.planes = 1; L.p1.planes = 3;
   L.in0 = n0; L.in1 = n1; L.XSin = n0 + 3 * n1;
   L.tp_numel = woff;
-  build_layer_common(m, prefix, in_blocks, s_in, L, n0, n1);
+  build_layer_common(mem, m, prefix, in_blocks, s_in, L, n0, n1);
   {  // static scale of h~ (bounded by the radial MLP's first layer: build_layer_common)
     int ex = 0;
     std::frexp(0.5 * (double)L.dg.hmax2, &ex);
@@ -516,7 +498,7 @@ LayerDev build_layer_separable(const jamun_model& m, const std::string& prefix, 
 
 }  // namespace
 
-LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
+LayerDev build_layer(DevArena& mem, DevArena& dg_mem, const jamun_model& m, const std::string& prefix, const std::vector<InBlock>& in_blocks,
                      const std::vector<double>& s_in, int n_slices,
                      const std::vector<float>* uniq_rows, int row_len, bool pack_dg, const std::vector<float>* all_rows, bool wide) {
   const jamun_hparams& hp = m.hp;
@@ -539,7 +521,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
         (lo == 0 ? sum0 : sum1) += in_blocks[b].mul;
       }
   L.tp_numel = off;
-  if (hp.separable) return build_layer_separable(m, prefix, in_blocks, s_in, L);
+  if (hp.separable) return build_layer_separable(mem, m, prefix, in_blocks, s_in, L);
   const auto& W3 = m.get(prefix + ".gated_conv.f.f.radial_nn.3.weight", off * H);
   const auto& b3 = m.get(prefix + ".gated_conv.f.f.radial_nn.3.bias", off);
   const double c0 = std::sqrt(1.0 / sum0), c1 = sum1 > 0 ? std::sqrt(3.0 / sum1) : 0.0;
@@ -588,13 +570,13 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
     blocks1.push_back(b);
   }
   if (wide) {  // the wide path (jamun_wide.hip): k_conv_wide's chunking, no specialised kernels
-    L.p0 = pack_problem(blocks0, 1, G0, n_slices, JAMUN_WIDE_KSUB0, W3, b3, H, true);
-    L.p1 = pack_problem(blocks1, 3, G1, n_slices, JAMUN_WIDE_KSUB1, W3, b3, H, true);
-    build_layer_common(m, prefix, in_blocks, s_in, L, in0, in1, true);
+    L.p0 = pack_problem(mem, blocks0, 1, G0, n_slices, JAMUN_WIDE_KSUB0, W3, b3, H, true);
+    L.p1 = pack_problem(mem, blocks1, 3, G1, n_slices, JAMUN_WIDE_KSUB1, W3, b3, H, true);
+    build_layer_common(mem, m, prefix, in_blocks, s_in, L, in0, in1, true);
     return L;
   }
-  L.p0 = pack_problem(blocks0, 1, G0, n_slices, JAMUN_KSUB0, W3, b3, H);
-  L.p1 = pack_problem(blocks1, 3, G1, n_slices, JAMUN_KSUB1, W3, b3, H);
+  L.p0 = pack_problem(mem, blocks0, 1, G0, n_slices, JAMUN_KSUB0, W3, b3, H);
+  L.p1 = pack_problem(mem, blocks1, 3, G1, n_slices, JAMUN_KSUB1, W3, b3, H);
 
   bool x0_contig = true;
   for (size_t i = 1; i < x0ve.size(); ++i) x0_contig = x0_contig && x0ve[i].xoff == x0ve[0].xoff + (int)i;
@@ -652,10 +634,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
           wt[((size_t)k * 15 + g) * 64 + lane] = make_float4(v[0], v[1], v[2], v[3]);
         }
     }
-    L.dg.wx = dev_upload(wx);
-    L.dg.wd = dev_upload(wd);
-    L.dg.wv = dev_upload(wv);
-    L.dg.wt = dev_upload(wt);
+    L.dg.wx = dg_mem.upload(wx); L.dg.wd = dg_mem.upload(wd); L.dg.wv = dg_mem.upload(wv); L.dg.wt = dg_mem.upload(wt);
     // f16x3 contraction: the same weights BALANCED by exact powers of two and split into hi + lo halves.  An f16 pair carries 22 bits
     // only while its lo half is a normal number, i.e. within 2^-14 .. 2^-17 of the largest value sharing its scale, and trained
     // checkpoints spread their channels over many octaves (a feature channel that is small has large weights, and the other way
@@ -702,8 +681,8 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
         std::vector<float> gx(216), gT(128, 1.f);
         for (int u = 0; u < 120; ++u) { gx[u] = (float)std::ldexp(1.0, e0[u]); gT[u] = (float)std::ldexp(1.0, eT[u]); }
         for (int u = 0; u < 32; ++u) for (int mm = 0; mm < 3; ++mm) gx[120 + 3 * u + mm] = (float)std::ldexp(1.0, e1[u]);
-        L.dg.gx = dev_upload(gx); L.dg.gT = dev_upload(gT);
-        L.dg.cf0 = dev_upload(cf0); L.dg.cf1 = dev_upload(cf1); L.dg.cfT = dev_upload(cfT);
+        L.dg.gx = dg_mem.upload(gx); L.dg.gT = dg_mem.upload(gT);
+        L.dg.cf0 = dg_mem.upload(cf0); L.dg.cf1 = dg_mem.upload(cf1); L.dg.cfT = dg_mem.upload(cfT);
       }
       L.dg.sB = 0;  // (the column factors carry the weight scales)
       std::vector<float4> wxh((size_t)n_k * 5 * 8 * 2 * 64), wdh((size_t)n_k * 5 * 2 * 2 * 64), wvh((size_t)n_k * 2 * 2 * 2 * 64);
@@ -763,7 +742,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
           if (w < 2) copy_blocks(wdh, (((size_t)k * 5 + 4) * 2 + w) * 2, base + 28);
           for (int G = 0; G < 2; ++G) copy_blocks(wvh, (((size_t)k * 2 + (w >> 1)) * 2 + G) * 2, base + 30 + 2 * G);
         }
-      L.dg.wxh = dev_upload(wh);
+      L.dg.wxh = dg_mem.upload(wh);
       // T pre-pass (k_tprod_h): scalar inputs -> vector rows, weights as the A operand of v_mfma_f32_32x32x16_f16
       {
         L.dg.sBt = 0;  // (balanced per input channel (gT) and per column (cfT), as the contraction's weights)
@@ -780,7 +759,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
               const size_t b = ((size_t)k * 16 + 2 * g) * 64 + lane;
               pack8(v, wth[b], wth[b + 64]);
             }
-        L.dg.wth = dev_upload(wth);
+        L.dg.wth = dg_mem.upload(wth);
       }
       // jamun_conv_mf.hip: the A operand of the contraction is the ACCUMULATOR of the forming MFMA (lane = destination, registers =
       // channels), so half p of lane (column c, hh) in K-step s2 is input u = 16 s2 + (p & 3) + 8 (p >> 2) + 4 hh of the wave's 32
@@ -831,7 +810,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
                 }
           }
         }
-        L.dg.wm = dev_upload(wm);
+        L.dg.wm = dg_mem.upload(wm);
         // tail tiles (k_tail_contract): the vector outputs take x1, cross AND the scalar channels times v_m (no T pre-pass there) in one
         // accumulator, so the three weight blocks share one column scale; 24 blocks per hidden unit: x1 (2 K-steps x hi, lo), cross,
         // then the scalar channel tiles w = 0..3 (input gauge e0: the rows are staged once, with the conv kernel's channel factors)
@@ -865,8 +844,8 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
                   pack8(v, wmt[b], wmt[b + 64]);
                 }
             }
-          L.dg.wmt = dev_upload(wmt);
-          L.dg.cf1t = dev_upload(cf1t);
+          L.dg.wmt = dg_mem.upload(wmt);
+          L.dg.cf1t = dg_mem.upload(cf1t);
         }
       }
     }
@@ -914,7 +893,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
               out[128 + 2 * u + 1] = in[32 * NT0 + u];
             }
           }
-        L.tt2 = dev_upload(tt2);
+        L.tt2 = mem.upload(tt2);
       }
       if (NT0 == 5 && G0 <= 160 && G1 <= 32 && U <= 128) {
         const int UT = U <= 32 ? 1 : (U <= 64 ? 2 : 4);
@@ -944,7 +923,7 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
                 const size_t b = (((size_t)k * 6 + r) * 4 * UT + 4 * ut + 2 * s2) * 64 + lane;
                 pack8(v, tw[b], tw[b + 64]);
               }
-        L.tabw = dev_upload(tw);
+        L.tabw = mem.upload(tw);
       }
     }
   }
@@ -1024,11 +1003,53 @@ LayerDev build_layer(const jamun_model& m, const std::string& prefix, const std:
         xph[w] |= (unsigned)hi << sh;
         xpl[w] |= (unsigned)lo << sh;
       }
-    L.wx = dev_upload(wx);
-    L.xph = dev_upload(xph); L.xpl = dev_upload(xpl);
-    L.xcf0 = dev_upload(cf0); L.xcf1 = dev_upload(cf1);
+    L.wx = mem.upload(wx);
+    L.xph = mem.upload(xph); L.xpl = mem.upload(xpl);
+    L.xcf0 = mem.upload(cf0); L.xcf1 = mem.upload(cf1);
   }
 
-  build_layer_common(m, prefix, in_blocks, s_in, L, in0, in1);
+  build_layer_common(mem, m, prefix, in_blocks, s_in, L, in0, in1);
   return L;
+}
+
+// ---- head (EquivariantMLP, _mlp.py:84-114) and output gain (e3conv.py:134-135)
+void pack_head(const jamun_model& m, jamun_sampler* s) {
+  const int mul0 = m.hp.mul0, mul1 = m.hp.mul1, G0 = mul0 + mul1;
+  const auto& Wl = m.get("output_head.0.lin.weight", (int64_t)mul0 * G0 + (int64_t)mul1 * mul1);
+  const auto& Wo = m.get("output_head.1.weight", mul1);
+  const auto& gain = m.get("output_gain", 1);
+  std::vector<float> wg((size_t)mul0 * mul1), wv((size_t)mul1 * mul1), wo(mul1);
+  for (int u = 0; u < mul0; ++u)
+    for (int w = 0; w < mul1; ++w) wg[(size_t)u * mul1 + w] = (float)((double)Wl[(size_t)u * G0 + mul0 + w] / std::sqrt((double)mul0));
+  for (int i = 0; i < mul1 * mul1; ++i) wv[i] = (float)((double)Wl[(size_t)mul0 * G0 + i] / std::sqrt((double)mul1));
+  for (int w = 0; w < mul1; ++w) wo[w] = (float)((double)Wo[w] / std::sqrt((double)mul1) * (double)gain[0]);
+  s->w_gate = s->mem.upload(wg); s->w_vec = s->mem.upload(wv); s->w_out = s->mem.upload(wo);
+}
+
+// f16x3 radial MLP (k_edge_h16): W1's radial part per layer scaled to the top of the f16 range and split hi + lo, as A fragments
+void pack_edge_h16(jamun_sampler* s) {
+  std::vector<float4> w1h;
+  std::vector<float> isc;
+  for (auto& L : s->layers) {
+    double wmax = 0;
+    for (float v : L.w1r_h) wmax = std::max(wmax, (double)std::fabs(v));
+    int ex = 0;
+    if (wmax > 0 && std::isfinite(wmax)) std::frexp(wmax, &ex);
+    const int sW = std::max(-40, std::min(40, 14 - ex));
+    isc.push_back((float)std::ldexp(1.0, -14 - sW));
+    const double sc = std::ldexp(1.0, sW);
+    for (int mt = 0; mt < 2; ++mt)
+      for (int s2 = 0; s2 < 2; ++s2) {
+        std::vector<float4> hi(64), lo(64);
+        for (int lane = 0; lane < 64; ++lane) {
+          const int hh = lane >> 5, k = 32 * mt + (lane & 31);
+          double v[8];
+          for (int j = 0; j < 8; ++j) v[j] = (double)L.w1r_h[(size_t)(16 * s2 + 8 * hh + j) * 64 + k] * sc;  // w1r: [basis][hidden]
+          pack8(v, hi[lane], lo[lane]);
+        }
+        w1h.insert(w1h.end(), hi.begin(), hi.end());
+        w1h.insert(w1h.end(), lo.begin(), lo.end());
+      }
+  }
+  s->w1h_all = s->mem.upload(w1h); s->w1isc_all = s->mem.upload(isc);
 }

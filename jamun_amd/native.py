@@ -332,6 +332,13 @@ def plan_segments(cus: int, ng: int, n_k: int, n_atoms: int, tile_atoms, tile_ch
     return {"segs": segs, "max_segs": ms.value, "n_slabs": nsl.value, "atom_nslab": nslab[:n_atoms].copy()}
 
 
+def live_allocations() -> tuple:
+    """``jamun_debug_live_allocations``: (number, bytes) of the device and pinned buffers the library holds in this process."""
+    n, b = C.c_int64(), C.c_int64()
+    _lib.check(_lib.load().jamun_debug_live_allocations(C.byref(n), C.byref(b)))
+    return n.value, b.value
+
+
 # ---- stand-alone operators --------------------------------------------------------------------------------------
 
 

@@ -92,6 +92,23 @@ def test_library_reads_no_environment_and_tuning_is_validated():
     assert fields == [n for n, _ in _lib.jamun_tuning._fields_]  # the binding mirrors the header field for field
 
 
+def test_host_sources_allocate_device_memory_through_the_arena_only():
+    """hipMalloc / hipFree / hipHostMalloc / hipHostFree occur in the host sources (csrc/*.cpp, csrc/*.h) inside `class DevArena`
+    (jamun_host.h) and nowhere else: no buffer can be allocated without an owner that frees it."""
+    csrc = os.path.join(ROOT, "jamun_amd", "csrc")
+    calls = re.compile(r"\bhip(?:Host)?(?:Malloc|Free)\b")
+    hdr = open(os.path.join(csrc, "jamun_host.h")).read()
+    start = hdr.index("class DevArena {")
+    end = hdr.index("\n};\n", start)
+    assert len(calls.findall(hdr[start:end])) == 4  # the arena is where they are
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".cpp", ".h")):
+            txt = open(os.path.join(csrc, f)).read()
+            if f == "jamun_host.h":
+                txt = txt[:start] + txt[end:]
+            assert not calls.findall(txt), f
+
+
 def _device_isa(src: str) -> str:
     """gfx950 ISA text of one kernel source with the library's own flags (hipcc -S --cuda-device-only), cached under csrc/build/ by the same
     digest as the objects (source + shared headers + flags)."""
