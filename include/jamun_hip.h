@@ -252,6 +252,18 @@ int jamun_encode_pdb_models(const float* xyz_dev, int64_t frame_stride, int64_t 
 int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, uint8_t* out_dev,
                             int64_t out_capacity, void* stream);
 
+/* ---- superposition: frames -> frames aligned on a reference structure, and their RMSD to it ---------------------------------------------
+ * What mdtraj's Trajectory.superpose does per frame, on the device.  Frames are addressed as the encoders above address them (frame and
+ * atom strides in floats, components adjacent), input and output with their own strides; ref_dev [n_atoms, 3] is contiguous.  For every
+ * frame: out = R (x - centroid(x)) + centroid(ref) with the PROPER rotation R (det +1, never a reflection) that minimises
+ * sum_i |out_i - ref_i|^2 (Horn's quaternion method), and rmsd_dev[frame] = sqrt(mean_i |out_i - ref_i|^2) computed from the values written.
+ * rmsd_dev may be NULL.  out_dev may be xyz_dev itself if the strides are equal too (in place); any other overlap of the memory the two
+ * views span is JAMUN_ERR_INVALID.  n_atoms == 1: out = ref, rmsd = 0.  Rank-deficient frames (two atoms, collinear atoms) get a rigid image
+ * with the minimal RMSD; the rotation about the free axis is arbitrary.  A frame with a non-finite value yields a non-finite frame and rmsd
+ * and leaves the other frames alone.  Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation. */
+int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* ref_dev,
+                           float* out_dev, int64_t out_frame_stride, int64_t out_atom_stride, float* rmsd_dev, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

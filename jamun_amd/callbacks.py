@@ -60,11 +60,18 @@ class SaveTrajectoryCallback:
     chunks of frames through fixed staging memory on one side stream) and ``joined.pdb`` / ``joined.dcd`` are EXTENDED by the new
     chains' frames; the files are byte for byte those of ``"host"``.  ``"auto"`` (default) takes the device path when the sample
     tensors are on a GPU, the native library loads and no process group is initialised (the multi-rank gather delivers host
-    blocks: it keeps the host path), else the host path.  ``.npy`` files are written from the host copy either way."""
+    blocks: it keeps the host path), else the host path.  ``.npy`` files are written from the host copy either way.
+
+    ``superpose=True`` writes every ``.pdb`` / ``.dcd`` frame (per chain and ``joined``) superposed on the label's reference structure,
+    its dataset molecule's ``pos`` — the init structure, what the reference's consumers align on (``dataset.trajectory[0]``,
+    ``metrics/_visualize_samples.py:26-28``): the best proper rotation and translation per frame (`superpose.superpose_host`; on the
+    device path ``jamun_superpose.hip`` on the encoder's side stream, in front of the encoders).  The ``.npy`` files stay the raw
+    sampler output (the lossless record), and ``predicted_samples/rmsd/<i>.npy`` (float32 ``[T]``, nm: each frame's RMSD to the reference
+    after the fit) and ``rmsd/joined.npy`` (their concatenation) appear.  Off (default) nothing changes."""
 
     def __init__(self, datasets: Sequence, sample_key: str = "xhat_traj", output_dir: str = "sampler", write_pdb: bool = True,
                  write_dcd: bool = True, save_true_trajectory: bool = False, npy_index_restarts_per_batch: bool = False,
-                 async_write: bool = True, encode: str = "auto", **_):
+                 async_write: bool = True, encode: str = "auto", superpose: bool = False, **_):
         if encode not in ("auto", "host", "device"):
             raise ValueError(f"encode must be 'auto', 'host' or 'device', got {encode!r}")
         self.encode = encode
@@ -97,6 +104,18 @@ class SaveTrajectoryCallback:
         self._encoder = None  # traj_encode.DeviceTrajectoryEncoder, created with the first device-encoded batch
         self._dev_blocks: dict = {}  # (label, first chain index) -> (device block [chains, n, T, 3], event recorded behind its producer)
         self._joined_frames = {l: 0 for l in self.labels}  # models / frames in joined.pdb / joined.dcd
+        self.superpose = bool(superpose)
+        self._ref: Dict[str, np.ndarray] = {}  # superpose: per label the reference structure [n, 3] (float32, nm)
+        self._ref_dev: dict = {}  # ... and its device copy, made on the encoder's stream with the first device-encoded batch
+        self._rmsd: Dict[str, List[np.ndarray]] = {l: [] for l in self.labels}  # ... and per chain the RMSD of its frames, [T] each
+        if self.superpose:
+            for label in self.labels:
+                mol = getattr(self.datasets[label], "molecule", None)
+                if mol is None or mol.get("pos") is None:
+                    raise ValueError(f"SaveTrajectoryCallback(superpose=True): the dataset of label {label!r} has no molecule, so no reference "
+                                     "structure to superpose on")
+                pos = mol["pos"]
+                self._ref[label] = np.ascontiguousarray(pos.detach().cpu().numpy() if torch.is_tensor(pos) else pos, dtype=np.float32)
 
     def _dir(self, label: str, ext: str) -> str:
         d = os.path.join(self.output_dir, label, "predicted_samples", ext)
@@ -111,6 +130,10 @@ class SaveTrajectoryCallback:
         if extension not in ("npy", "pdb", "dcd"):
             raise ValueError(f"Invalid extension: {extension}")
         return os.path.join(self._dir(label, extension), f"{trajectory_index}.{extension}")
+
+    def filename_rmsd(self, label: str, trajectory_index) -> str:
+        """``predicted_samples/rmsd/<i>.npy`` (superpose=True): float32 [T], the frames' RMSD in nm to the reference structure."""
+        return os.path.join(self._dir(label, "rmsd"), f"{trajectory_index}.npy")
 
     def on_sample_start(self, sampler):
         if not sampler.is_global_zero:
@@ -142,11 +165,22 @@ class SaveTrajectoryCallback:
 
         np.save(self.filename_pred(label, index if npy_index is None else npy_index, "npy"), arr)
         frames = np.transpose(arr, (1, 0, 2))  # "atoms frames coords -> frames atoms coords" (utils/mdtraj.py:17-21)
+        if self.superpose:  # (the .npy above stays the raw sampler output)
+            frames, rmsd = self._superposed(label, frames)
+            np.save(self.filename_rmsd(label, index), rmsd)
+            if index != "joined":
+                self._rmsd[label].append(rmsd)  # (kept per chain: a later batch on the device path extends rmsd/joined.npy from these)
         mol = self._mol(label)
         if self.write_pdb and mol is not None:
             save_pdb(self.filename_pred(label, index, "pdb"), mol, frames)
         if self.write_dcd:
             save_dcd(self.filename_pred(label, index, "dcd"), frames)
+
+    def _superposed(self, label: str, frames: np.ndarray):
+        """frames [T, n, 3] -> (the frames superposed on the label's reference structure, their RMSD to it [T]) on the host."""
+        from .superpose import superpose_host
+
+        return superpose_host(frames, self._ref[label])
 
     def _finished_writer_error(self) -> Optional[BaseException]:
         """A writer failure (disk full, permission, bad shape) must stop the run at the NEXT batch, not after the last one.  It is
@@ -262,8 +296,22 @@ class SaveTrajectoryCallback:
             for path in (joined_pdb, joined_dcd):
                 if os.path.exists(path):
                     os.unlink(path)
-        host_frames = lambda arr: np.transpose(arr, (1, 0, 2))
+        def host_frames(arr):  # [n, T, 3] -> [T, n, 3] for the host writers: superposed when the device frames are
+            frames = np.transpose(arr, (1, 0, 2))
+            return self._superposed(label, frames)[0] if self.superpose else frames
+
         joined_pdb_stale = False
+        ref_dev, align_chunk = None, 0
+        if self.superpose:
+            if self._ref[label].shape[0] != n:
+                raise ValueError(f"superpose: the reference structure of {label!r} has {self._ref[label].shape[0]} atoms, the samples have {n}")
+            if self._ref_dev.get(label) is None or self._ref_dev[label].device != enc.device:
+                with torch.cuda.device(enc.device), torch.cuda.stream(enc.stream):
+                    self._ref_dev[label] = torch.from_numpy(self._ref[label]).to(enc.device)
+            ref_dev = self._ref_dev[label]
+            align_chunk = enc.align_frames_per_chunk(n)
+            if align_chunk == 0:  # (one frame larger than the scratch: the host writers, on host-superposed frames)
+                pdb_chunk = dcd_chunk = 0
 
         def both(*sinks):
             def sink(data):
@@ -278,18 +326,36 @@ class SaveTrajectoryCallback:
                 if os.path.exists(path):
                     os.unlink(path)
             jobs = []
+            spans = [(0, T, frames)]  # (first frame, end, the [end - first, n, 3] device view the encoders read)
+            rmsd = None
+            if align_chunk > 0:  # superposed chunk by chunk into the encoder's scratch; the RMSD leaves as the chunk's bytes
+                rmsd = np.empty(T, dtype=np.float32)
+                spans = [(s0, min(T, s0 + align_chunk), enc.align_view(n, min(T, s0 + align_chunk) - s0)) for s0 in range(0, T, align_chunk)]
+
+                def keep_rmsd(data, a, b, r=rmsd):
+                    r[a:b] = np.frombuffer(data, dtype=np.float32)
+
             if pdb_chunk > 0:
                 enc.reset_unencodable()
-                for t0 in range(0, T, pdb_chunk):
-                    t1 = min(T, t0 + pdb_chunk)
-                    jobs.append((enc.encode_pdb(frames[t0:t1], t0, *tmpl), lambda data, p=own_pdb: append_pdb_models(p, data)))
-                    jobs.append((enc.encode_pdb(frames[t0:t1], joined_at + t0, *tmpl), lambda data: append_pdb_models(joined_pdb, data)))
-            if dcd_chunk > 0:
-                for t0 in range(0, T, dcd_chunk):
-                    t1 = min(T, t0 + dcd_chunk)
-                    jobs.append((enc.encode_dcd(frames[t0:t1]), both(lambda data, p=own_dcd, k=t1 - t0: append_dcd_frames(p, n, data, k),
-                                                                     lambda data, k=t1 - t0: append_dcd_frames(joined_dcd, n, data, k))))
+            for s0, s1, view in spans:
+                if rmsd is not None:
+                    jobs.append((enc.superpose(frames[s0:s1], ref_dev, view), lambda data, a=s0, b=s1: keep_rmsd(data, a, b)))
+                if pdb_chunk > 0:
+                    for t0 in range(s0, s1, pdb_chunk):
+                        t1 = min(s1, t0 + pdb_chunk)
+                        jobs.append((enc.encode_pdb(view[t0 - s0 : t1 - s0], t0, *tmpl), lambda data, p=own_pdb: append_pdb_models(p, data)))
+                        jobs.append((enc.encode_pdb(view[t0 - s0 : t1 - s0], joined_at + t0, *tmpl), lambda data: append_pdb_models(joined_pdb, data)))
+                if dcd_chunk > 0:
+                    for t0 in range(s0, s1, dcd_chunk):
+                        t1 = min(s1, t0 + dcd_chunk)
+                        jobs.append((enc.encode_dcd(view[t0 - s0 : t1 - s0]), both(lambda data, p=own_dcd, k=t1 - t0: append_dcd_frames(p, n, data, k),
+                                                                                 lambda data, k=t1 - t0: append_dcd_frames(joined_dcd, n, data, k))))
             enc.run(jobs)
+            if self.superpose:
+                if rmsd is None:
+                    rmsd = self._superposed(label, np.transpose(arr, (1, 0, 2)))[1]
+                np.save(self.filename_rmsd(label, i), rmsd)
+                self._rmsd[label].append(rmsd)
             if pdb_chunk > 0 and enc.unencodable() != 0:
                 save_pdb(own_pdb, mol, host_frames(arr))
                 joined_pdb_stale = True
@@ -303,6 +369,8 @@ class SaveTrajectoryCallback:
             save_pdb(joined_pdb, mol, host_frames(np.concatenate(self.chains[label], axis=1)))
         if self.write_dcd and dcd_chunk == 0:
             save_dcd(joined_dcd, host_frames(np.concatenate(self.chains[label], axis=1)))
+        if self.superpose:
+            np.save(self.filename_rmsd(label, "joined"), np.concatenate(self._rmsd[label]))
 
     def _submit(self, fn, *args) -> None:
         if not self.async_write:  # a failed synchronous write surfaces at the next batch too, through the same gather

@@ -1098,6 +1098,36 @@ int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t 
   });
 }
 
+// ---- superposition (jamun_superpose.hip) -------------------------------------------------------------------------------------------------
+
+namespace {
+// floats spanned by a [n_frames, n_atoms, 3] view: one past its last component (n_frames, n_atoms >= 1)
+unsigned __int128 view_span(int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames) {
+  return (unsigned __int128)(n_frames - 1) * (unsigned __int128)frame_stride + (unsigned __int128)(n_atoms - 1) * (unsigned __int128)atom_stride + 3;
+}
+}  // namespace
+
+int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* ref_dev,
+                           float* out_dev, int64_t out_frame_stride, int64_t out_atom_stride, float* rmsd_dev, void* stream) {
+  return guarded([&] {
+    if (!xyz_dev || !ref_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (frame_stride < 0 || atom_stride < 0 || out_frame_stride < 0 || out_atom_stride < 0 || n_atoms < 0 || n_frames < 0)
+      throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (n_frames == 0 || n_atoms == 0) return;  // (no frame, or frames without atoms: nothing to write, no RMSD to define)
+    const bool in_place = out_dev == xyz_dev && out_frame_stride == frame_stride && out_atom_stride == atom_stride;
+    if (!in_place) {
+      const unsigned __int128 a0 = reinterpret_cast<uintptr_t>(xyz_dev), b0 = reinterpret_cast<uintptr_t>(out_dev);
+      const unsigned __int128 a1 = a0 + 4 * view_span(frame_stride, atom_stride, n_atoms, n_frames);
+      const unsigned __int128 b1 = b0 + 4 * view_span(out_frame_stride, out_atom_stride, n_atoms, n_frames);
+      if (a0 < b1 && b0 < a1)
+        throw Err(JAMUN_ERR_INVALID, "out_dev overlaps xyz_dev: the output may be the input itself with the same strides (in place), or memory apart from it");
+    }
+    launch_superpose_frames(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, ref_dev, out_dev, out_frame_stride, out_atom_stride, rmsd_dev,
+                            (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int jamun_build_edges(jamun_sampler* s, const float* y_dev, void* stream) {
   return guarded([&] {
     if (!s || !y_dev) throw Err(JAMUN_ERR_INVALID, "null argument");

@@ -507,3 +507,6 @@ long long pdb_models_nbytes(long long body_len, long long first_model, long long
 void launch_encode_pdb(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, long long first_model,
                        const unsigned char* body, int body_len, const int* coord_off, unsigned char* out, unsigned int* unencodable, hipStream_t st);
 void launch_encode_dcd(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, unsigned char* out, hipStream_t st);
+// jamun_superpose.hip — rigid superposition of frames on a reference structure, per-frame RMSD
+void launch_superpose_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* ref, float* out,
+                             long long out_frame_stride, long long out_atom_stride, float* rmsd, hipStream_t st);

@@ -505,3 +505,37 @@ def encode_dcd_frames(xyz: torch.Tensor, out: torch.Tensor) -> int:
     with torch.cuda.device(xyz.device):
         _lib.check(lib.jamun_encode_dcd_frames(_ptr(xyz), fs, as_, n, T, _ptr(out), int(out.numel()), _stream()))
     return T * 3 * (4 * n + 8)
+
+
+# ---- superposition (jamun_superpose.hip) ----------------------------------------------------------------------------------------------
+
+def superpose_frames(frames: torch.Tensor, ref: torch.Tensor, out: Optional[torch.Tensor] = None, rmsd: Optional[torch.Tensor] = None,
+                     want_rmsd: bool = True):
+    """Queue the superposition of the frames ``frames [T, n, 3]`` (device fp32, a view of either trajectory layout) on ``ref [n, 3]`` on
+    the current stream: returns ``(aligned [T, n, 3], rmsd [T])``, each frame rotated (properly) and translated onto ``ref`` with the
+    least RMSD, and that RMSD.  ``out`` receives the aligned frames (default: a new tensor with the layout of ``frames``); it may be
+    ``frames`` itself.  ``rmsd`` (contiguous float32 [T]) receives the RMSD (default: a new tensor); ``want_rmsd=False`` passes no RMSD
+    buffer and returns ``None`` for it.  See ``jamun_superpose_frames``."""
+    lib = _lib.load()
+    fs, as_, n, T = _frame_strides(frames)
+    if n > 0x7FFFFFFF or T > 0x7FFFFFFF:
+        raise RuntimeError(f"{T} frames of {n} atoms: both counts must fit 31 bits")
+    if not ref.is_cuda or ref.device != frames.device or ref.dtype != torch.float32 or tuple(ref.shape) != (n, 3):
+        raise RuntimeError(f"ref must be a float32 [{n}, 3] tensor on {frames.device}, got {ref.dtype} {tuple(ref.shape)} on {ref.device}")
+    ref = ref.contiguous()
+    if out is None:
+        out = torch.empty_like(frames)  # (keeps the strides of a dense view such as a transposed chain)
+    if out.device != frames.device or tuple(out.shape) != tuple(frames.shape):
+        raise RuntimeError(f"out must be a [{T}, {n}, 3] tensor on {frames.device}, got {tuple(out.shape)} on {out.device}")
+    ofs, oas, _, _ = _frame_strides(out)
+    if not want_rmsd:
+        rmsd = None
+    elif rmsd is None:
+        rmsd = torch.empty(T, dtype=torch.float32, device=frames.device)
+    elif rmsd.device != frames.device or rmsd.dtype != torch.float32 or tuple(rmsd.shape) != (T,) or not rmsd.is_contiguous():
+        raise RuntimeError(f"rmsd must be a contiguous float32 [{T}] tensor on {frames.device}")
+    with torch.cuda.device(frames.device):
+        if rmsd is not None and n == 0:
+            rmsd.zero_()  # (frames without atoms: the call writes nothing)
+        _lib.check(lib.jamun_superpose_frames(_ptr(frames), fs, as_, n, T, _ptr(ref), _ptr(out), ofs, oas, _ptr(rmsd), _stream()))
+    return out, rmsd

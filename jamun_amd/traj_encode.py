@@ -6,6 +6,12 @@ one device buffer and two page-locked host buffers of ``STAGING_BYTES`` each, wh
 20 000-step batch of 256 dipeptides is ~9 GB of PDB text and is never resident.  While one page-locked buffer is written to the
 file, the next chunk is encoded and copied into the other.  All device work runs on ONE side stream (the walk keeps the
 current one).  `pdb.save_pdb` / `pdb.save_dcd` remain the specification of the bytes and the fallback.
+
+With ``SaveTrajectoryCallback(superpose=True)`` the frames are superposed on the reference structure on the same stream, in front of
+the encoders (``jamun_superpose_frames``), into ONE more device buffer of ``STAGING_BYTES`` that exists only then: a chain goes through
+it in chunks of ``align_frames_per_chunk`` frames (32 MiB hold 96 000 frames of a 29-atom molecule: a 20 000-frame chain is one chunk),
+each chunk aligned once and read by the encoders of all its files.  The RMSD of a chunk leaves through the staging buffers like any
+encoded chunk.  The memory is fixed whatever the number of frames: `staging_bytes` reports it.
 """
 
 from __future__ import annotations
@@ -31,10 +37,11 @@ class DeviceTrajectoryEncoder:
             self._counter = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._host = [p.numpy() for p in self._pinned]
         self._templates: Dict[int, Tuple[dict, torch.Tensor, torch.Tensor]] = {}
+        self._aligned = None  # float32 scratch of STAGING_BYTES for superposed frames, allocated with the first `align_view`
 
     def staging_bytes(self) -> int:
         """Bytes of staging memory this encoder holds (device + page-locked)."""
-        return int(self._dev.numel() + sum(p.numel() for p in self._pinned))
+        return int(self._dev.numel() + sum(p.numel() for p in self._pinned) + (4 * self._aligned.numel() if self._aligned is not None else 0))
 
     def template(self, mol: dict) -> Tuple[torch.Tensor, torch.Tensor]:
         """`pdb.pdb_model_template` of ``mol`` on the device, built once per molecule."""
@@ -69,6 +76,28 @@ class DeviceTrajectoryEncoder:
     @staticmethod
     def encode_dcd(frames: torch.Tensor) -> Callable[[torch.Tensor], int]:
         return lambda out: native.encode_dcd_frames(frames, out)
+
+    @staticmethod
+    def align_frames_per_chunk(n_atoms: int) -> int:
+        """Frames of ``n_atoms`` atoms the scratch of `align_view` holds (and whose RMSD, 4 bytes each, fits a staging buffer)."""
+        return min(STAGING_BYTES // (12 * n_atoms), STAGING_BYTES // 4) if n_atoms > 0 else 0
+
+    def align_view(self, n_atoms: int, n_frames: int) -> torch.Tensor:
+        """A ``[n_frames, n_atoms, 3]`` view of the scratch for superposed frames, laid out like a chain (``[n, T, 3]``: the frames of an
+        atom adjacent, so one lane per frame writes and reads it coalesced)."""
+        if self._aligned is None:
+            with torch.cuda.device(self.device):
+                self._aligned = torch.empty(STAGING_BYTES // 4, dtype=torch.float32, device=self.device)
+        if 3 * n_atoms * n_frames > self._aligned.numel():
+            raise RuntimeError(f"{n_frames} frames of {n_atoms} atoms do not fit the {4 * self._aligned.numel()}-byte scratch")
+        return self._aligned[: 3 * n_atoms * n_frames].view(n_atoms, n_frames, 3).transpose(0, 1)
+
+    @staticmethod
+    def superpose(frames: torch.Tensor, ref: torch.Tensor, aligned: torch.Tensor) -> Callable[[torch.Tensor], int]:
+        """A job for `run`: ``frames`` superposed on ``ref`` into ``aligned`` (a view of `align_view`); the job's bytes are the float32
+        RMSD of the frames."""
+        k = int(frames.shape[0])
+        return lambda out: (native.superpose_frames(frames, ref, out=aligned, rmsd=out[: 4 * k].view(torch.float32)), 4 * k)[1]
 
     def run(self, jobs: Iterable[Tuple[Callable[[torch.Tensor], int], Callable[[memoryview], None]]]) -> None:
         """``jobs``: (encode, sink) pairs, one per chunk.  ``encode(out)`` queues a kernel that fills the device staging buffer and

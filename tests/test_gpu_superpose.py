@@ -1,0 +1,257 @@
+"""GPU tests of the superposition kernel (jamun_superpose.hip: k_superpose_frames) and of ``SaveTrajectoryCallback(superpose=True)`` on
+the device path.  Expected values come from the fp64 reference of _superpose_cases.py (Horn's method through numpy's eigh), never from
+the kernel; test_superpose_host.py holds the premises (conditioning of the cases, a float32 model of the algorithm within half the bound)."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _superpose_cases as sc
+from _traj_molecules import dipeptide
+
+pytestmark = pytest.mark.gpu
+
+RMSD_TOL_NM = sc.RMSD_TOL_NM
+SENTINEL = 12345.0
+
+
+def _dev():
+    assert torch.cuda.is_available(), "these tests need a GPU"
+    return torch.device("cuda", 0)
+
+
+def _cycled(a: np.ndarray, T: int) -> np.ndarray:
+    return a[np.arange(T) % a.shape[0]]
+
+
+def _chain_view(frames: np.ndarray, dev, fill=float("nan")) -> torch.Tensor:
+    """``frames`` [T, n, 3] as the callback sees a chain: ``block[1].transpose(0, 1)`` of a 3-chain [chains, n, T, 3] block (no copy)."""
+    T, n, _ = frames.shape
+    block = torch.full((3, n, T, 3), fill, dtype=torch.float32, device=dev)
+    block[1] = torch.from_numpy(np.array(np.transpose(frames, (1, 0, 2)), order="C")).to(dev)  # (a writable copy)
+    view = block[1].transpose(0, 1)
+    assert view.shape == (T, n, 3) and view.data_ptr() == block[1].data_ptr()
+    return view
+
+
+def _check(got, got_rmsd, aligned, rmsd, what):
+    dc = float(sc.frame_rmsd(got, aligned).max())
+    dr = float(np.abs(got_rmsd.astype(np.float64) - rmsd).max()) if got_rmsd is not None else 0.0
+    print(f"{what}: kernel vs fp64 reference: coordinates {dc:.2e} nm, rmsd {dr:.2e} nm")
+    assert dc <= RMSD_TOL_NM and dr <= RMSD_TOL_NM, (what, dc, dr)
+
+
+# ------------------------------------------------------------------------------------------- the kernel against the fp64 reference
+
+@pytest.mark.parametrize("name", sc.COORD_MOLECULES)
+def test_every_frame_of_every_kind_matches_the_reference(name):
+    """All frames of a molecule (noisy, identity, half turns, rigid, mirror) as a strided chain view; the output goes into chain 1 of a
+    sentinel block whose other chains must stay untouched.  chain300 takes the second reference tile."""
+    from jamun_amd import native
+
+    dev = _dev()
+    pos, frames, (aligned, rmsd, g) = sc.case(name)
+    T, n = frames.shape[0], frames.shape[1]
+    out_block = torch.full((3, n, T, 3), SENTINEL, dtype=torch.float32, device=dev)
+    got, got_rmsd = native.superpose_frames(_chain_view(frames, dev), torch.from_numpy(pos.copy()).to(dev), out=out_block[1].transpose(0, 1))
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out_block[1].data_ptr() and got_rmsd.shape == (T,) and got_rmsd.dtype == torch.float32
+    host = out_block.cpu().numpy()
+    assert (host[0] == SENTINEL).all() and (host[2] == SENTINEL).all()
+    got, got_rmsd = np.transpose(host[1], (1, 0, 2)), got_rmsd.cpu().numpy()
+    _check(got, got_rmsd, aligned, rmsd, name)
+    sl = sc.kind_slices(name)
+    # the special frames by name: identity and exact half turns give pos back, the mirror image has the reference's rmsd
+    for kind in ("identity", "turn180", "rigid"):
+        assert sc.frame_rmsd(got[sl[kind]], np.broadcast_to(pos, got[sl[kind]].shape)).max() <= RMSD_TOL_NM, kind
+        assert got_rmsd[sl[kind]].max() <= RMSD_TOL_NM, kind
+    assert np.abs(got_rmsd[sl["mirror"]] - rmsd[sl["mirror"]]).max() <= RMSD_TOL_NM
+    if name in sc.CHIRAL_MOLECULES:
+        assert got_rmsd[sl["mirror"]].min() > 100 * RMSD_TOL_NM
+        assert np.abs(sc.pair_distances(got[sl["mirror"]]) - sc.pair_distances(pos[None])).max() <= 10 * RMSD_TOL_NM  # rotated, not reflected
+
+
+@pytest.mark.parametrize("T", [1, 63, 64, 65, 257])
+def test_frame_counts_around_a_wave_in_both_layouts_in_place_and_without_rmsd(T):
+    """A partial wave, exactly one, one frame over, several workgroups: the strided chain view and a contiguous [T, n, 3] tensor, out of
+    place, in place (same strides) and without an RMSD buffer give the same bits, within the bound of the reference."""
+    from jamun_amd import native
+
+    dev = _dev()
+    pos, frames, (aligned, rmsd, g) = sc.case("chain33")
+    frames, aligned, rmsd = _cycled(frames, T), _cycled(aligned, T), _cycled(rmsd, T)
+    ref = torch.from_numpy(pos.copy()).to(dev)
+    chain = _chain_view(frames, dev)
+    a_chain, r_chain = native.superpose_frames(chain, ref)
+    assert a_chain.stride() == chain.stride() or T == 1  # (the output of a chain view is laid out like the chain)
+    flat = torch.from_numpy(frames.copy()).to(dev)
+    assert flat.is_contiguous()
+    a_flat, r_flat = native.superpose_frames(flat, ref)
+    a_norm, none = native.superpose_frames(flat, ref, want_rmsd=False)
+    assert none is None
+    work = chain.clone(memory_format=torch.preserve_format)
+    a_in, r_in = native.superpose_frames(work, ref, out=work)
+    torch.cuda.synchronize()
+    assert a_in.data_ptr() == work.data_ptr()
+    _check(a_chain.cpu().numpy(), r_chain.cpu().numpy(), aligned, rmsd, f"chain view, T = {T}")
+    for other, other_r in ((a_flat, r_flat), (a_in, r_in), (a_norm, None)):
+        assert torch.equal(other, a_chain) and (other_r is None or torch.equal(other_r, r_chain))
+    if T > 1:
+        with pytest.raises(RuntimeError, match="overlaps"):  # the input's memory with other strides
+            native.superpose_frames(chain, ref, out=chain.transpose(0, 1).reshape(T, 33, 3))
+
+
+@pytest.mark.parametrize("name", sc.RANK_DEFICIENT)
+def test_rank_deficient_molecules_rmsd_and_pairwise_distances(name):
+    from jamun_amd import native
+
+    dev = _dev()
+    pos, frames, (aligned, rmsd, g) = sc.case(name)
+    got, got_rmsd = native.superpose_frames(_chain_view(frames, dev), torch.from_numpy(pos.copy()).to(dev))
+    got, got_rmsd = got.cpu().numpy(), got_rmsd.cpu().numpy()
+    assert np.isfinite(got).all()
+    assert np.abs(got_rmsd - rmsd).max() <= RMSD_TOL_NM
+    assert np.abs(sc.pair_distances(got) - sc.pair_distances(frames)).max() <= RMSD_TOL_NM
+    if pos.shape[0] == 1:  # one atom: the reference itself, rmsd exactly 0
+        assert np.array_equal(got, np.broadcast_to(pos, got.shape)) and not got_rmsd.any()
+
+
+# ------------------------------------------------------------------------------------------------------ isolation and stream order
+
+def test_a_non_finite_frame_leaves_its_neighbours_alone():
+    from jamun_amd import native
+
+    dev = _dev()
+    pos, frames, _ = sc.case("dipeptide")
+    ref = torch.from_numpy(pos.copy()).to(dev)
+    clean, clean_rmsd = native.superpose_frames(_chain_view(frames, dev), ref)
+    poked = frames.copy()
+    poked[7, 3, 1] = np.nan          # between two good frames of the same wave
+    poked[20, 0, 0] = np.inf
+    got, got_rmsd = native.superpose_frames(_chain_view(poked, dev), ref)
+    torch.cuda.synchronize()
+    keep = [t for t in range(frames.shape[0]) if t not in (7, 20)]
+    assert torch.equal(got[keep], clean[keep]) and torch.equal(got_rmsd[keep], clean_rmsd[keep])  # bit for bit
+    for t in (7, 20):
+        assert not torch.isfinite(got[t]).any() and not torch.isfinite(got_rmsd[t])
+
+
+def test_a_side_stream_call_is_ordered_behind_the_producer_of_its_input():
+    from jamun_amd import native
+
+    dev = _dev()
+    pos, frames, (aligned, rmsd, g) = sc.case("chain33")
+    frames, aligned, rmsd = _cycled(frames, 257), _cycled(aligned, 257), _cycled(rmsd, 257)
+    ref = torch.from_numpy(pos.copy()).to(dev)
+    half = torch.from_numpy(np.ascontiguousarray(np.transpose(frames, (1, 0, 2))) * np.float32(0.5)).to(dev)  # [n, T, 3]
+    busy = torch.randn(2048, 2048, device=dev)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(dev)
+    with torch.cuda.stream(side):
+        for _ in range(8):
+            busy = busy @ busy * 1e-3  # work in front of the producer, so that an unordered kernel would read the input too early
+        chain = half + half            # exact: the frames, produced on the side stream
+        got, got_rmsd = native.superpose_frames(chain.transpose(0, 1), ref)
+    side.synchronize()
+    _check(got.cpu().numpy(), got_rmsd.cpu().numpy(), aligned, rmsd, "side stream")
+
+
+def test_public_call_takes_the_kernel_for_device_tensors():
+    from jamun_amd import native
+    from jamun_amd.superpose import superpose
+
+    dev = _dev()
+    pos, frames, (aligned, rmsd, g) = sc.case("dipeptide")
+    x, ref = torch.from_numpy(frames.copy()).to(dev), torch.from_numpy(pos.copy()).to(dev)
+    a, r = superpose(x, ref)
+    b, s = native.superpose_frames(x, ref)
+    assert a.is_cuda and torch.equal(a, b) and torch.equal(r, s)
+    _check(a.cpu().numpy(), r.cpu().numpy(), aligned, rmsd, "superpose()")
+
+
+# ------------------------------------------------------------------------------------------------- the callback on the device path
+
+def _tumbling_batches(mol, dev, chains, T, n_batches, seed):
+    """Samples as `unbatch_samples` hands them out ([n, T, 3] views of one [T, sum N, 3] device tensor): tumbling noisy images of pos."""
+    rng = np.random.RandomState(seed)
+    pos = mol["pos"].numpy().astype(np.float64)
+    n = pos.shape[0]
+    out = []
+    for _ in range(n_batches):
+        traj = np.empty((T, chains * n, 3), dtype=np.float32)
+        for c in range(chains):
+            rot = sc.random_rotations(rng, T)
+            traj[:, c * n : (c + 1) * n] = np.einsum("fab,ib->fia", rot, pos) + rng.uniform(-0.5, 0.5, size=(T, 1, 3)) + sc.SIGMA * rng.randn(T, n, 3)
+        traj = torch.from_numpy(traj).to(dev)
+        out.append([{"dataset_label": "m", "atom_type_index": mol["atom_type_index"], "xhat_traj": traj[:, c * n : (c + 1) * n].permute(1, 0, 2)}
+                    for c in range(chains)])
+    return out
+
+
+def _run(cb, batches, dev):
+    smp = sc.CaseSampler(dev)
+    cb.on_sample_start(smp)
+    for b in batches:
+        cb.on_after_sample_batch(b, smp)
+        cb.flush()
+    cb.on_sample_end(smp)
+    return cb
+
+
+@pytest.mark.parametrize("small_staging", [False, True], ids=["staging_default", "staging_4k"])
+def test_callback_device_path_writes_the_host_path_files(tmp_path, monkeypatch, small_staging):
+    """3 chains of the dipeptide x 70 frames, two batches.  With 4 KiB of staging a chain is aligned in three chunks (34 frames each)
+    and every chunk encoded in several pieces."""
+    from jamun_amd import traj_encode
+    from jamun_amd.callbacks import SaveTrajectoryCallback
+
+    if small_staging:
+        monkeypatch.setattr(traj_encode, "STAGING_BYTES", 1 << 12)
+    dev = _dev()
+    mol = dipeptide()
+    n, T, chains = 10, 70, 3
+    batches = _tumbling_batches(mol, dev, chains, T, 2, seed=5)
+    ds = sc.CaseDataset(mol, "m")
+    cbs = {m: _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / m), encode=m, superpose=True), batches, dev) for m in ("device", "host")}
+    raw = _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "raw"), encode="device"), batches, dev)
+    assert cbs["device"]._encoder is not None and cbs["host"]._encoder is None
+    trees = {m: sc.tree(str(tmp_path / m)) for m in ("device", "host", "raw")}
+    assert sorted(trees["device"]) == sorted(trees["host"])
+    assert sorted(f for f in trees["device"] if "rmsd" not in f) == sorted(trees["raw"])
+    for f, data in trees["device"].items():
+        if f.endswith(".npy") and "rmsd" not in f:
+            assert data == trees["raw"][f] == trees["host"][f], f  # the raw sampler output, whatever the option
+    names = [str(i) for i in range(2 * chains)] + ["joined"]
+    for name in names:
+        frames = 2 * chains * T if name == "joined" else T
+        d, h = (tmp_path / m / "m" / "predicted_samples" for m in ("device", "host"))
+        got, want = sc.read_dcd_nm(str(d / "dcd" / f"{name}.dcd"), n), sc.read_dcd_nm(str(h / "dcd" / f"{name}.dcd"), n)
+        assert got.shape == want.shape == (frames, n, 3)
+        dev_dcd = float(sc.frame_rmsd(got, want).max())
+        got_r, want_r = np.load(d / "rmsd" / f"{name}.npy"), np.load(h / "rmsd" / f"{name}.npy")
+        assert got_r.dtype == np.float32 and got_r.shape == want_r.shape == (frames,)
+        dev_r = float(np.abs(got_r - want_r).max())
+        pdb_units = int(np.abs(sc.read_pdb_milli_angstrom(str(d / "pdb" / f"{name}.pdb"), n) - sc.read_pdb_milli_angstrom(str(h / "pdb" / f"{name}.pdb"), n)).max())
+        print(f"{name}: device vs host files: dcd {dev_dcd:.2e} nm, rmsd {dev_r:.2e} nm, pdb {pdb_units} x 1e-3 Angstrom")
+        assert dev_dcd <= RMSD_TOL_NM and dev_r <= RMSD_TOL_NM and pdb_units <= 1
+        assert 0.01 < want_r.min() and want_r.max() < 0.1  # the frames were fitted: what is left is the noise, not the tumbling
+    assert np.array_equal(np.load(tmp_path / "device" / "m" / "predicted_samples" / "rmsd" / "joined.npy"),
+                          np.concatenate([np.load(tmp_path / "device" / "m" / "predicted_samples" / "rmsd" / f"{i}.npy") for i in range(2 * chains)]))
+    assert cbs["device"]._encoder.staging_bytes() == 4 * traj_encode.STAGING_BYTES and raw._encoder.staging_bytes() == 3 * traj_encode.STAGING_BYTES
+
+
+def test_staging_memory_does_not_depend_on_the_frame_count(tmp_path):
+    from jamun_amd import traj_encode
+    from jamun_amd.callbacks import SaveTrajectoryCallback
+
+    dev = _dev()
+    mol = dipeptide()
+    sizes = []
+    for T in (70, 700):
+        cb = _run(SaveTrajectoryCallback([sc.CaseDataset(mol, "m")], output_dir=str(tmp_path / str(T)), encode="device", superpose=True),
+                  _tumbling_batches(mol, dev, 3, T, 1, seed=T), dev)
+        sizes.append(cb._encoder.staging_bytes())
+        assert cb._encoder._aligned.numel() * 4 == traj_encode.STAGING_BYTES and not cb._dev_blocks
+        assert np.load(tmp_path / str(T) / "m" / "predicted_samples" / "rmsd" / "joined.npy").shape == (3 * T,)
+    assert sizes == [4 * traj_encode.STAGING_BYTES] * 2
