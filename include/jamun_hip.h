@@ -264,6 +264,26 @@ int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t 
 int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* ref_dev,
                            float* out_dev, int64_t out_frame_stride, int64_t out_atom_stride, float* rmsd_dev, void* stream);
 
+/* ---- internal coordinates: frames -> distances, bond angles and dihedrals of listed atoms -------------------------------------------------
+ * What mdtraj's compute_distances / compute_angles / compute_dihedrals (and so compute_phi / compute_psi / compute_chi*) give per frame, on
+ * the device.  Frames are addressed as the encoders above address them (frame and atom strides in floats, components adjacent).  idx_dev
+ * [n_feat][4] int32 is the feature table: the number of LEADING non-negative entries of a row decides the feature (the rest are -1):
+ *   2  distance   |p1 - p0|  (nm)
+ *   3  bond angle at p1   atan2(|a x b|, a.b), a = p0 - p1, b = p2 - p1, in [0, pi]
+ *   4  dihedral   b1 = p1 - p0, b2 = p2 - p1, b3 = p3 - p2, c1 = b2 x b3, c2 = b1 x b2: atan2((b1.c1) |b2|, c1.c2) in (-pi, pi] (IUPAC sign)
+ *   0 or 1, or any of the leading entries >= n_atoms: NaN; such a row reads nothing.
+ * out_dev is contiguous fp32 [n_frames][W]:
+ *   cossin == 0   W = n_feat:    out[t][j] = the value of feature j in frame t
+ *   cossin != 0   W = 2 n_feat:  out[t][2 j] = cos, out[t][2 j + 1] = sin of feature j's angle or dihedral, taken from the two atan2 arguments
+ *                                (x, y) / |(x, y)| (not cos(atan2(..)): continuous across +-pi); a distance gives (d, 0), a NaN feature (NaN, NaN).
+ * fp32 throughout, the differences formed first.  A non-finite coordinate makes exactly the features that use its atom in its frame NaN;
+ * every other value is bit for bit what it is without it.  Degenerate geometry (coincident atoms, a collinear triple inside a dihedral) gives
+ * what atan2f gives for the rounded arguments (atan2f(0, +-0) = 0 or pi; cos / sin = (+-1, 0)): finite for finite coordinates below 1e9 nm.
+ * out_capacity (in floats) below n_frames * W is JAMUN_ERR_INVALID and nothing is written; n_feat == 0 or n_frames == 0 launches nothing and
+ * succeeds.  Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation. */
+int jamun_internal_coords(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames,
+                          const int32_t* idx_dev, int32_t n_feat, int32_t cossin, float* out_dev, int64_t out_capacity, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

@@ -67,13 +67,29 @@ class SaveTrajectoryCallback:
     ``metrics/_visualize_samples.py:26-28``): the best proper rotation and translation per frame (`superpose.superpose_host`; on the
     device path ``jamun_superpose.hip`` on the encoder's side stream, in front of the encoders).  The ``.npy`` files stay the raw
     sampler output (the lossless record), and ``predicted_samples/rmsd/<i>.npy`` (float32 ``[T]``, nm: each frame's RMSD to the reference
-    after the fit) and ``rmsd/joined.npy`` (their concatenation) appear.  Off (default) nothing changes."""
+    after the fit) and ``rmsd/joined.npy`` (their concatenation) appear.  Off (default) nothing changes.
+
+    ``torsions`` adds the torsion angles of every frame: ``True`` or ``"backbone"`` phi, psi and omega, ``"all"`` the side-chain chi1..chi4
+    besides (`features.torsion_indices`: by atom names, mdtraj's rule; the dataset's molecule must carry names).  Per label
+    ``<label>/torsion_labels.json`` (the labels and atom indices of the F columns) and ``predicted_samples/torsions/<i>.npy`` (float32
+    ``[T, F]``, radians, dihedrals in (-pi, pi]) per chain, ``torsions/joined.npy`` their concatenation over all chains so far on axis 0.
+    The values come from the raw sampler output (internal coordinates do not change under superposition: the files are the same with
+    ``superpose`` on and off): `features.internal_coords_host` on the host path, ``jamun_intcoord.hip`` on the encoder's side stream on the
+    device path.  Off (``False``, default) nothing changes."""
 
     def __init__(self, datasets: Sequence, sample_key: str = "xhat_traj", output_dir: str = "sampler", write_pdb: bool = True,
                  write_dcd: bool = True, save_true_trajectory: bool = False, npy_index_restarts_per_batch: bool = False,
-                 async_write: bool = True, encode: str = "auto", superpose: bool = False, **_):
+                 async_write: bool = True, encode: str = "auto", superpose: bool = False, torsions=False, **_):
         if encode not in ("auto", "host", "device"):
             raise ValueError(f"encode must be 'auto', 'host' or 'device', got {encode!r}")
+        if torsions is None or torsions is False:
+            self.torsions = None
+        elif torsions is True or torsions == "backbone":
+            self.torsions = "backbone"
+        elif torsions == "all":
+            self.torsions = "all"
+        else:
+            raise ValueError(f"torsions must be False, True, 'backbone' or 'all', got {torsions!r}")
         self.encode = encode
         labels = []
         self.datasets = {}
@@ -116,6 +132,18 @@ class SaveTrajectoryCallback:
                                      "structure to superpose on")
                 pos = mol["pos"]
                 self._ref[label] = np.ascontiguousarray(pos.detach().cpu().numpy() if torch.is_tensor(pos) else pos, dtype=np.float32)
+        self._tor_index: Dict[str, np.ndarray] = {}  # torsions: per label the index table int32 [F, 4] ...
+        self._tor_labels: Dict[str, List[str]] = {}  # ... the labels of its rows ...
+        self._tor_index_dev: dict = {}  # ... its device copy, made on the encoder's stream with the first device-encoded batch
+        self._tor: Dict[str, List[np.ndarray]] = {l: [] for l in self.labels}  # ... and per chain the torsions of its frames, [T, F] each
+        if self.torsions is not None:
+            from .features import torsion_indices
+
+            for label in self.labels:
+                mol = getattr(self.datasets[label], "molecule", None)
+                if mol is None:
+                    raise ValueError(f"SaveTrajectoryCallback(torsions={torsions!r}): the dataset of label {label!r} has no molecule to find torsions in")
+                self._tor_index[label], self._tor_labels[label] = torsion_indices(mol, backbone=True, sidechain=self.torsions == "all")
 
     def _dir(self, label: str, ext: str) -> str:
         d = os.path.join(self.output_dir, label, "predicted_samples", ext)
@@ -135,6 +163,16 @@ class SaveTrajectoryCallback:
         """``predicted_samples/rmsd/<i>.npy`` (superpose=True): float32 [T], the frames' RMSD in nm to the reference structure."""
         return os.path.join(self._dir(label, "rmsd"), f"{trajectory_index}.npy")
 
+    def filename_torsions(self, label: str, trajectory_index) -> str:
+        """``predicted_samples/torsions/<i>.npy`` (torsions on): float32 [T, F], the frames' torsion angles in radians."""
+        return os.path.join(self._dir(label, "torsions"), f"{trajectory_index}.npy")
+
+    def _torsions_host(self, label: str, frames: np.ndarray) -> np.ndarray:
+        """frames [T, n, 3] (raw) -> their torsions float32 [T, F] on the host."""
+        from .features import internal_coords_host
+
+        return internal_coords_host(frames, self._tor_index[label]).astype(np.float32)
+
     def on_sample_start(self, sampler):
         if not sampler.is_global_zero:
             return
@@ -143,6 +181,9 @@ class SaveTrajectoryCallback:
         for label in self.labels:
             for ext in ("npy", "pdb", "dcd"):
                 self._dir(label, ext)
+            if self.torsions is not None:
+                with open(os.path.join(self.output_dir, label, "torsion_labels.json"), "w") as f:
+                    json.dump({"labels": self._tor_labels[label], "atom_indices": self._tor_index[label].tolist(), "unit": "rad"}, f, indent=1)
             mol = self._mol(label)
             if mol is not None and self.write_pdb:  # topology from the dataset's first frame (_save_trajectory.py:53-56)
                 save_pdb(os.path.join(self.output_dir, label, "topology.pdb"), mol, mol["pos"][None])
@@ -165,6 +206,10 @@ class SaveTrajectoryCallback:
 
         np.save(self.filename_pred(label, index if npy_index is None else npy_index, "npy"), arr)
         frames = np.transpose(arr, (1, 0, 2))  # "atoms frames coords -> frames atoms coords" (utils/mdtraj.py:17-21)
+        if self.torsions is not None:  # (of the raw frames; joined = the chains' arrays, kept as _rmsd keeps them)
+            if index != "joined":
+                self._tor[label].append(self._torsions_host(label, frames))
+            np.save(self.filename_torsions(label, index), np.concatenate(self._tor[label]) if index == "joined" else self._tor[label][-1])
         if self.superpose:  # (the .npy above stays the raw sampler output)
             frames, rmsd = self._superposed(label, frames)
             np.save(self.filename_rmsd(label, index), rmsd)
@@ -224,7 +269,7 @@ class SaveTrajectoryCallback:
 
     def on_after_sample_batch(self, sample: Sequence[dict], sampler):
         error = self._finished_writer_error()
-        use_device = self._use_device_encoder(sample) and (self.write_dcd or self.write_pdb)
+        use_device = self._use_device_encoder(sample) and (self.write_dcd or self.write_pdb or self.torsions is not None)
         for s in sample:
             if s.get("dataset_label") not in self.datasets:
                 raise KeyError(f"sample dataset label {s.get('dataset_label')!r} has no dataset")
@@ -313,6 +358,18 @@ class SaveTrajectoryCallback:
             if align_chunk == 0:  # (one frame larger than the scratch: the host writers, on host-superposed frames)
                 pdb_chunk = dcd_chunk = 0
 
+        tor_index_dev, tor_width, tor_chunk = None, 0, 0
+        if self.torsions is not None:
+            tor_width = int(self._tor_index[label].shape[0])
+            if tor_width > 0 and int(self._tor_index[label].max()) >= n:
+                raise ValueError(f"torsions: the molecule of {label!r} names atom {int(self._tor_index[label].max())}, the samples have {n} atoms")
+            tor_chunk = enc.features_frames_per_chunk(tor_width)  # (0: no torsion, or one frame's torsions larger than the staging buffer)
+            if tor_chunk > 0:
+                if self._tor_index_dev.get(label) is None or self._tor_index_dev[label].device != enc.device:
+                    with torch.cuda.device(enc.device), torch.cuda.stream(enc.stream):
+                        self._tor_index_dev[label] = torch.from_numpy(self._tor_index[label]).to(enc.device)
+                tor_index_dev = self._tor_index_dev[label]
+
         def both(*sinks):
             def sink(data):
                 for fn in sinks:
@@ -350,7 +407,22 @@ class SaveTrajectoryCallback:
                         t1 = min(s1, t0 + dcd_chunk)
                         jobs.append((enc.encode_dcd(view[t0 - s0 : t1 - s0]), both(lambda data, p=own_dcd, k=t1 - t0: append_dcd_frames(p, n, data, k),
                                                                                  lambda data, k=t1 - t0: append_dcd_frames(joined_dcd, n, data, k))))
+            tor = None
+            if tor_chunk > 0:  # torsions of the RAW chain, chunk by chunk straight into the staging buffer
+                tor = np.empty((T, tor_width), dtype=np.float32)
+
+                def keep_tor(data, a, b, dst=tor):
+                    dst[a:b] = np.frombuffer(data, dtype=np.float32).reshape(b - a, tor_width)
+
+                for t0 in range(0, T, tor_chunk):
+                    t1 = min(T, t0 + tor_chunk)
+                    jobs.append((enc.features(frames[t0:t1], tor_index_dev), lambda data, a=t0, b=t1, fn=keep_tor: fn(data, a, b)))
             enc.run(jobs)
+            if self.torsions is not None:
+                if tor is None:  # (F = 0: [T, 0]; or the host formulas)
+                    tor = self._torsions_host(label, np.transpose(arr, (1, 0, 2)))
+                np.save(self.filename_torsions(label, i), tor)
+                self._tor[label].append(tor)
             if self.superpose:
                 if rmsd is None:
                     rmsd = self._superposed(label, np.transpose(arr, (1, 0, 2)))[1]
@@ -371,6 +443,8 @@ class SaveTrajectoryCallback:
             save_dcd(joined_dcd, host_frames(np.concatenate(self.chains[label], axis=1)))
         if self.superpose:
             np.save(self.filename_rmsd(label, "joined"), np.concatenate(self._rmsd[label]))
+        if self.torsions is not None:
+            np.save(self.filename_torsions(label, "joined"), np.concatenate(self._tor[label]))
 
     def _submit(self, fn, *args) -> None:
         if not self.async_write:  # a failed synchronous write surfaces at the next batch too, through the same gather

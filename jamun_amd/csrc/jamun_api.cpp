@@ -1128,6 +1128,23 @@ int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t a
   });
 }
 
+// ---- internal coordinates (jamun_intcoord.hip) ---------------------------------------------------------------------------------------------
+
+int jamun_internal_coords(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const int32_t* idx_dev,
+                          int32_t n_feat, int32_t cossin, float* out_dev, int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    if (frame_stride < 0 || atom_stride < 0 || n_atoms < 0 || n_frames < 0 || n_feat < 0 || out_capacity < 0)
+      throw Err(JAMUN_ERR_INVALID, "negative argument");
+    const int64_t need = (int64_t)n_frames * (int64_t)n_feat * (cossin ? 2 : 1);  // (< 2^63: two 31-bit counts and a factor 2)
+    if (out_capacity < need)
+      throw Err(JAMUN_ERR_INVALID, "out_capacity " + std::to_string(out_capacity) + " is too small: the features need " + std::to_string(need) + " floats");
+    if (n_frames == 0 || n_feat == 0) return;  // (nothing to write)
+    if (!xyz_dev || !idx_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_internal_coords(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, idx_dev, n_feat, cossin != 0, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int jamun_build_edges(jamun_sampler* s, const float* y_dev, void* stream) {
   return guarded([&] {
     if (!s || !y_dev) throw Err(JAMUN_ERR_INVALID, "null argument");

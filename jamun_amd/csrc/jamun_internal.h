@@ -510,3 +510,7 @@ void launch_encode_dcd(const float* xyz, long long frame_stride, long long atom_
 // jamun_superpose.hip — rigid superposition of frames on a reference structure, per-frame RMSD
 void launch_superpose_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* ref, float* out,
                              long long out_frame_stride, long long out_atom_stride, float* rmsd, hipStream_t st);
+// jamun_intcoord.hip — internal coordinates of frames (distances, bond angles, dihedrals) from an index table; n_frames, n_feat >= 1
+#define JAMUN_INTCOORD_FTILE 16  // table rows a workgroup stages at a time (native.INTCOORD_FEATURE_TILE mirrors it for the tests)
+void launch_internal_coords(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const int* idx, int n_feat,
+                            int cossin, float* out, hipStream_t st);

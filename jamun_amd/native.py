@@ -11,6 +11,7 @@ import os
 import functools
 from typing import Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -539,3 +540,65 @@ def superpose_frames(frames: torch.Tensor, ref: torch.Tensor, out: Optional[torc
             rmsd.zero_()  # (frames without atoms: the call writes nothing)
         _lib.check(lib.jamun_superpose_frames(_ptr(frames), fs, as_, n, T, _ptr(ref), _ptr(out), ofs, oas, _ptr(rmsd), _stream()))
     return out, rmsd
+
+
+# ---- internal coordinates (jamun_intcoord.hip) ----------------------------------------------------------------------------------------
+
+INTCOORD_FEATURE_TILE = 16  # table rows a workgroup of k_internal_coords stages at a time (JAMUN_INTCOORD_FTILE, jamun_internal.h)
+
+
+def check_index_table(index, n_atoms: int) -> np.ndarray:
+    """The feature table of `internal_coords` checked on the host: an integer ``[F, 4]`` array (or tensor) whose rows are 2 to 4 atom
+    indices in ``[0, n_atoms)`` followed by ``-1`` up to four entries.  Returns it as contiguous int32; anything else is a ``ValueError``."""
+    if torch.is_tensor(index):
+        if index.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+            raise ValueError(f"the index table must hold integers, got {index.dtype}")
+        a = index.detach().cpu().numpy()
+    else:
+        a = np.asarray(index)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"the index table must hold integers, got {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError(f"the index table must have shape [F, 4], got {tuple(a.shape)}")
+    a = a.astype(np.int64)
+    valid = a >= 0
+    k = np.cumprod(valid, axis=1).sum(axis=1)  # leading non-negative entries of each row
+    tail = np.arange(4)[None, :] >= k[:, None]
+    bad = (k < 2) | ((a != -1) & tail).any(axis=1) | ((a >= n_atoms) & ~tail).any(axis=1)
+    if bad.any():
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"row {j} of the index table, {a[j].tolist()}, is not 2 to 4 atom indices in [0, {n_atoms}) followed by -1")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def internal_coords(frames: torch.Tensor, index, cossin: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the internal coordinates of the frames ``frames [T, n, 3]`` (device fp32, a view of either trajectory layout) on the current
+    stream: float32 ``[T, F]``, or ``[T, 2 F]`` interleaved (cos, sin) pairs with ``cossin`` (a distance as (d, 0)).  ``index [F, 4]``: per
+    row 2 (distance, nm), 3 (bond angle) or 4 (dihedral, mdtraj's sign) atom indices, then ``-1``.  A host table (array, list, CPU tensor) is
+    checked by `check_index_table` and uploaded; an int32 tensor already on the device of ``frames`` is taken as checked (upload once,
+    call often: the kernel answers an index out of range with NaN, it never reads there).  ``out`` (contiguous float32 of that shape on
+    the device) receives the result; default a new tensor.  See ``jamun_internal_coords``."""
+    if not torch.is_tensor(frames) or frames.ndim != 3 or frames.shape[2] != 3:
+        raise RuntimeError(f"frames must be a [frames, atoms, 3] tensor, got {tuple(getattr(frames, 'shape', ()))}")
+    on_device = torch.is_tensor(index) and index.is_cuda
+    if not on_device:
+        index = check_index_table(index, int(frames.shape[1]))  # (before anything needs a GPU)
+    fs, as_, n, T = _frame_strides(frames)
+    if n > 0x7FFFFFFF or T > 0x7FFFFFFF or int(index.shape[0]) > 0x7FFFFFFF:
+        raise RuntimeError(f"{T} frames of {n} atoms, {int(index.shape[0])} features: the counts must fit 31 bits")
+    lib = _lib.load()
+    if on_device:
+        if index.device != frames.device or index.dtype != torch.int32 or index.ndim != 2 or index.shape[1] != 4 or not index.is_contiguous():
+            raise ValueError(f"an index table on the device must be a contiguous int32 [F, 4] tensor on {frames.device}, "
+                             f"got {index.dtype} {tuple(index.shape)} on {index.device}")
+    else:
+        index = torch.from_numpy(index).to(frames.device)
+    F = int(index.shape[0])
+    W = 2 * F if cossin else F
+    if out is None:
+        out = torch.empty((T, W), dtype=torch.float32, device=frames.device)
+    elif out.device != frames.device or out.dtype != torch.float32 or tuple(out.shape) != (T, W) or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous float32 [{T}, {W}] tensor on {frames.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(frames.device):
+        _lib.check(lib.jamun_internal_coords(_ptr(frames), fs, as_, n, T, _ptr(index), F, 1 if cossin else 0, _ptr(out), int(out.numel()), _stream()))
+    return out

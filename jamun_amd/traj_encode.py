@@ -12,6 +12,11 @@ the encoders (``jamun_superpose_frames``), into ONE more device buffer of ``STAG
 it in chunks of ``align_frames_per_chunk`` frames (32 MiB hold 96 000 frames of a 29-atom molecule: a 20 000-frame chain is one chunk),
 each chunk aligned once and read by the encoders of all its files.  The RMSD of a chunk leaves through the staging buffers like any
 encoded chunk.  The memory is fixed whatever the number of frames: `staging_bytes` reports it.
+
+With ``SaveTrajectoryCallback(torsions=...)`` one more job per chunk of ``features_frames_per_chunk`` frames computes the torsion angles of
+the RAW frames (``jamun_internal_coords``: internal coordinates do not change under superposition) straight into the device staging
+buffer, behind the same event on the same stream; the sink copies the chunk into the chain's ``[T, F]`` array.  No buffer is added: the
+index table (16 bytes per torsion, uploaded once per label by the callback) is all the device memory the option costs.
 """
 
 from __future__ import annotations
@@ -98,6 +103,18 @@ class DeviceTrajectoryEncoder:
         RMSD of the frames."""
         k = int(frames.shape[0])
         return lambda out: (native.superpose_frames(frames, ref, out=aligned, rmsd=out[: 4 * k].view(torch.float32)), 4 * k)[1]
+
+    @staticmethod
+    def features_frames_per_chunk(width: int) -> int:
+        """Frames whose ``width`` float32 internal coordinates fit a staging buffer."""
+        return STAGING_BYTES // (4 * width) if width > 0 else 0
+
+    @staticmethod
+    def features(frames: torch.Tensor, index_dev: torch.Tensor, cossin: bool = False) -> Callable[[torch.Tensor], int]:
+        """A job for `run`: the internal coordinates of ``frames`` for the table ``index_dev`` (int32 [F, 4], on the device), written by the
+        kernel into the staging buffer itself; the job's bytes are the float32 ``[frames, W]`` block, W = F or 2 F."""
+        k, w = int(frames.shape[0]), int(index_dev.shape[0]) * (2 if cossin else 1)
+        return lambda out: (native.internal_coords(frames, index_dev, cossin=cossin, out=out[: 4 * k * w].view(torch.float32).view(k, w)), 4 * k * w)[1]
 
     def run(self, jobs: Iterable[Tuple[Callable[[torch.Tensor], int], Callable[[memoryview], None]]]) -> None:
         """``jobs``: (encode, sink) pairs, one per chunk.  ``encode(out)`` queues a kernel that fills the device staging buffer and
