@@ -284,6 +284,34 @@ int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t a
 int jamun_internal_coords(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames,
                           const int32_t* idx_dev, int32_t n_feat, int32_t cossin, float* out_dev, int64_t out_capacity, void* stream);
 
+/* ---- histograms of pairs of angle columns (Ramachandran plots) and their Jensen-Shannon divergence ----------------------------------------
+ * angles_dev is fp32 [n_frames] rows of `width` values, row_stride floats apart (what the entry above writes: row_stride = width).
+ * pairs_dev [n_pairs][2] int32 names the x and the y column of each histogram; edges_dev [bins + 1] fp64 holds the bin edges, ascending
+ * (numpy's linspace(-pi, pi, bins + 1) uploaded: the bins then are numpy's by construction); 1 <= bins <= 128.  `cuts` is a HOST array of
+ * n_cuts (1..64) frame counts, strictly ascending within [1, n_frames]; it is read before the call returns.  SEGMENT c holds the frames
+ * cuts[c-1] <= t < cuts[c] (cuts[-1] := 0):
+ *   counts_dev  uint32 [n_cuts][n_pairs][bins * bins]   bin (bx, by) at bx * bins + by: the frames of segment c whose (x, y) lie there.
+ *                                                        The value, promoted to fp64, is clipped to [edges[0], edges[bins]] first; its bin is
+ *                                                        the largest b <= bins - 1 with edges[b] <= value (the last edge is inclusive).
+ *   skipped_dev uint32 [n_cuts][n_pairs]                 the frames of segment c whose x or y is not finite; they are in no bin.
+ * Both outputs are zeroed by the call (on `stream`), so counts + skipped of a segment and pair add up to the segment's frames; a pair with
+ * a column outside [0, width) counts nothing (skipped included) and reads nothing.  Integer atomic adds: the result is exact and the same
+ * in every run.  counts_capacity (in counters) below n_cuts * n_pairs * bins * bins is JAMUN_ERR_INVALID, as is
+ * every argument outside the ranges above, and then nothing is written; n_pairs == 0 launches nothing and succeeds.
+ *
+ * The second entry turns such segment counts into the curve "divergence from a reference against the number of frames": for every cut c the
+ * PREFIX histogram (segments 0..c summed, uint64) is normalised and compared with the normalised reference ref_dev uint32
+ * [n_ref_pairs][bins * bins], n_ref_pairs = n_pairs or 1 (one reference for every pair):
+ *   per_pair_dev fp64 [n_cuts][n_pairs]   JSD(p, q) = (sum p log(p / m) + sum q log(q / m)) / 2, m = (p + q) / 2, in nats, 0 log 0 = 0
+ *   pooled_dev   fp64 [n_cuts]            the same with all pairs (and all reference pairs) summed into one histogram first
+ * fp64 throughout, summed in a fixed order: the value depends on the inputs alone.  A prefix or a reference without a count gives NaN.
+ * Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation. */
+int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_frames, int32_t width, const int32_t* pairs_dev, int32_t n_pairs,
+                       const double* edges_dev, int32_t bins, const int32_t* cuts, int32_t n_cuts, uint32_t* counts_dev,
+                       int64_t counts_capacity, uint32_t* skipped_dev, void* stream);
+int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pairs, int32_t bins, const uint32_t* ref_dev, int32_t n_ref_pairs,
+                        double* pooled_dev, double* per_pair_dev, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

@@ -519,6 +519,20 @@ class TrajectoryMetricCallback:
             meter.on_sample_end()
 
 
+class RamachandranMetricsCallback(TrajectoryMetricCallback):
+    """`TrajectoryMetricCallback` over `ramachandran.RamachandranMetrics` (the reference's ``RamachandranPlotMetricsCallback``,
+    ``callbacks/sampler/ramachandran.yaml``, without its plots): per chain and for the joined trajectory the (phi, psi) histograms and
+    the JS divergence from the true trajectory against the number of samples, under ``<output_dir>/<label>/ramachandran/``.  Keyword
+    arguments go to the meter (``bins``, ``pairing``, ``reference``, ``output_dir``, ``sample_key``, ``device``)."""
+
+    def __init__(self, datasets: Sequence, **kw):
+        import functools
+
+        from .ramachandran import RamachandranMetrics
+
+        super().__init__(datasets, functools.partial(RamachandranMetrics, **kw))
+
+
 class MeasureSamplingTimeCallback:
     """Wall time per batch and per sampled conformation (one saved (walker, frame) pair — the reference's unit,
     ``callbacks/sampler/_measure_sampling_time.py:57,71``).  Writes ``sampler/timing.json`` on rank 0."""

@@ -1145,6 +1145,56 @@ int jamun_internal_coords(const float* xyz_dev, int64_t frame_stride, int64_t at
   });
 }
 
+// ---- histograms of angle pairs and their Jensen-Shannon divergence (jamun_hist.hip) --------------------------------------------------------
+
+int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_frames, int32_t width, const int32_t* pairs_dev, int32_t n_pairs,
+                       const double* edges_dev, int32_t bins, const int32_t* cuts, int32_t n_cuts, uint32_t* counts_dev,
+                       int64_t counts_capacity, uint32_t* skipped_dev, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0 || width < 0 || n_pairs < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (bins < 1 || bins > JAMUN_HIST_MAX_BINS)
+      throw Err(JAMUN_ERR_INVALID, "bins " + std::to_string(bins) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_BINS) + "]");
+    if (n_cuts < 1 || n_cuts > JAMUN_HIST_MAX_CUTS)
+      throw Err(JAMUN_ERR_INVALID, "n_cuts " + std::to_string(n_cuts) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_CUTS) + "]");
+    if (!cuts) throw Err(JAMUN_ERR_INVALID, "null argument");
+    JamunHistCuts k;
+    k.n = n_cuts;
+    for (int c = 0; c < JAMUN_HIST_MAX_CUTS; ++c) k.cut[c] = c < n_cuts ? cuts[c] : 0;
+    for (int c = 0; c < n_cuts; ++c)
+      if (k.cut[c] < 1 || k.cut[c] > n_frames || (c > 0 && k.cut[c] <= k.cut[c - 1]))
+        throw Err(JAMUN_ERR_INVALID, "cuts[" + std::to_string(c) + "] = " + std::to_string(k.cut[c]) + ": the cuts must ascend strictly within [1, " +
+                                         std::to_string(n_frames) + "]");
+    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    if (n_pairs > 65535) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is above 65535");
+    const int64_t need = (int64_t)n_cuts * (int64_t)n_pairs * bins * bins;  // (< 2^37)
+    if (counts_capacity < need)
+      throw Err(JAMUN_ERR_INVALID, "counts_capacity " + std::to_string(counts_capacity) + " is too small: the histograms need " + std::to_string(need) + " counters");
+    if (n_pairs == 0) return;  // (nothing to write)
+    if (!angles_dev || !pairs_dev || !edges_dev || !counts_dev || !skipped_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHECK(hipMemsetAsync(counts_dev, 0, (size_t)need * sizeof(uint32_t), st));
+    HIPCHECK(hipMemsetAsync(skipped_dev, 0, (size_t)n_cuts * n_pairs * sizeof(uint32_t), st));
+    launch_hist2d_pairs(angles_dev, row_stride, width, pairs_dev, n_pairs, edges_dev, bins, k, counts_dev, skipped_dev, st);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pairs, int32_t bins, const uint32_t* ref_dev, int32_t n_ref_pairs,
+                        double* pooled_dev, double* per_pair_dev, void* stream) {
+  return guarded([&] {
+    if (bins < 1 || bins > JAMUN_HIST_MAX_BINS)
+      throw Err(JAMUN_ERR_INVALID, "bins " + std::to_string(bins) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_BINS) + "]");
+    if (n_cuts < 1 || n_cuts > JAMUN_HIST_MAX_CUTS)
+      throw Err(JAMUN_ERR_INVALID, "n_cuts " + std::to_string(n_cuts) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_CUTS) + "]");
+    if (n_pairs < 1 || n_pairs > 65534) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is outside [1, 65534]");
+    if (n_ref_pairs != 1 && n_ref_pairs != n_pairs)
+      throw Err(JAMUN_ERR_INVALID, "n_ref_pairs " + std::to_string(n_ref_pairs) + " is neither 1 nor n_pairs = " + std::to_string(n_pairs));
+    if (!counts_dev || !ref_dev || !pooled_dev || !per_pair_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_js_divergence(counts_dev, n_cuts, n_pairs, bins, ref_dev, n_ref_pairs, pooled_dev, per_pair_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int jamun_build_edges(jamun_sampler* s, const float* y_dev, void* stream) {
   return guarded([&] {
     if (!s || !y_dev) throw Err(JAMUN_ERR_INVALID, "null argument");

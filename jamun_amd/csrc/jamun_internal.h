@@ -514,3 +514,15 @@ void launch_superpose_frames(const float* xyz, long long frame_stride, long long
 #define JAMUN_INTCOORD_FTILE 16  // table rows a workgroup stages at a time (native.INTCOORD_FEATURE_TILE mirrors it for the tests)
 void launch_internal_coords(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const int* idx, int n_feat,
                             int cossin, float* out, hipStream_t st);
+// jamun_hist.hip — 2-D histograms of pairs of angle columns over segments of frames, and the Jensen-Shannon divergence of their prefixes
+#define JAMUN_HIST_SLICE 4096             // frames of a segment one workgroup counts (native.HIST_SLICE mirrors it for the tests)
+#define JAMUN_HIST_MAX_BINS 128           // bins per axis: 128 * 128 uint32 counters are the 64 KB of LDS a workgroup may ask for
+#define JAMUN_HIST_MAX_CUTS 64
+struct JamunHistCuts {  // the cuts travel in the kernel arguments
+  int n;
+  int cut[JAMUN_HIST_MAX_CUTS];
+};
+void launch_hist2d_pairs(const float* angles, long long row_stride, int width, const int* pairs, int n_pairs, const double* edges, int bins,
+                         const JamunHistCuts& cuts, unsigned* counts, unsigned* skipped, hipStream_t st);
+void launch_js_divergence(const unsigned* counts, int n_cuts, int n_pairs, int bins, const unsigned* ref, int n_ref_pairs, double* pooled,
+                          double* per_pair, hipStream_t st);

@@ -602,3 +602,115 @@ def internal_coords(frames: torch.Tensor, index, cossin: bool = False, out: Opti
     with torch.cuda.device(frames.device):
         _lib.check(lib.jamun_internal_coords(_ptr(frames), fs, as_, n, T, _ptr(index), F, 1 if cossin else 0, _ptr(out), int(out.numel()), _stream()))
     return out
+
+
+# ---- histograms of angle pairs and their Jensen-Shannon divergence (jamun_hist.hip) -------------------------------------------------------
+
+HIST_SLICE = 4096    # frames of a segment one workgroup of k_hist2d_pairs counts (JAMUN_HIST_SLICE, jamun_internal.h)
+HIST_MAX_BINS = 128  # bins per axis the kernel takes (JAMUN_HIST_MAX_BINS: 128 * 128 counters are 64 KB of LDS)
+HIST_MAX_CUTS = 64   # JAMUN_HIST_MAX_CUTS
+
+_hist_edges: Dict[Tuple[str, int], torch.Tensor] = {}  # (device, bins) -> the uploaded edges
+
+
+def hist_edges(bins: int) -> np.ndarray:
+    """The bin edges of both axes, float64 ``[bins + 1]``: what ``np.histogram2d(..., bins, range=((-pi, pi), (-pi, pi)))`` uses."""
+    return np.linspace(-np.pi, np.pi, int(bins) + 1)
+
+
+def check_hist_args(n_frames: int, width: int, pairs, bins, cuts) -> Tuple[Optional[np.ndarray], int, np.ndarray]:
+    """The arguments of `hist2d_pairs` checked on the host; ``ValueError`` for: ``pairs`` not an integer ``[P, 2]`` table of columns in
+    ``[0, width)`` (``None`` stands for a table already on the device, taken as checked), ``bins`` not an integer in ``[1, 128]``,
+    ``cuts`` not 1 to 64 integers ascending strictly within ``[1, n_frames]``.  Returns ``(pairs int32 [P, 2] or None, bins, cuts int32 [C])``."""
+    if pairs is not None:
+        a = pairs.detach().cpu().numpy() if torch.is_tensor(pairs) else np.asarray(pairs)
+        if a.size == 0:
+            a = a.reshape(-1, 2).astype(np.int64)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"pairs must hold integers, got {a.dtype}")
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"pairs must have shape [P, 2], got {tuple(a.shape)}")
+        a = a.astype(np.int64)
+        bad = ((a < 0) | (a >= width)).any(axis=1)
+        if bad.any():
+            j = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"row {j} of pairs, {a[j].tolist()}, is not two columns in [0, {width})")
+        pairs = np.ascontiguousarray(a, dtype=np.int32)
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= HIST_MAX_BINS:
+        raise ValueError(f"bins must be an integer in [1, {HIST_MAX_BINS}], got {bins!r}")
+    c = np.asarray(cuts.detach().cpu().numpy() if torch.is_tensor(cuts) else cuts)
+    if c.ndim != 1 or c.dtype.kind not in "iu" or not 1 <= c.shape[0] <= HIST_MAX_CUTS:
+        raise ValueError(f"cuts must be 1 to {HIST_MAX_CUTS} integers, got {c.dtype} {tuple(c.shape)}")
+    c = c.astype(np.int64)
+    if c[0] < 1 or c[-1] > n_frames or (np.diff(c) <= 0).any():
+        raise ValueError(f"cuts must ascend strictly within [1, {n_frames}], got {c.tolist()}")
+    return pairs, int(bins), np.ascontiguousarray(c, dtype=np.int32)
+
+
+def hist2d_pairs(angles: torch.Tensor, pairs, bins: int, cuts, out: Optional[torch.Tensor] = None,
+                 skipped: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Queue the segment histograms of ``angles [T, W]`` (device fp32 with adjacent columns: what `internal_coords` returns, or a view of
+    it with a row stride) on the current stream: ``(counts uint32-valued int32 [C, P, bins, bins], skipped int32 [C, P])``; segment ``c``
+    holds the frames ``cuts[c-1] <= t < cuts[c]``.  The rule of every bin is `ramachandran.histogram_host`'s, integer for integer.
+    ``pairs [P, 2]`` (x column, y column): a host table is checked and uploaded, an int32 tensor on the device of ``angles`` is taken as
+    checked (a column out of range there counts nothing).  The arguments are checked before anything needs a GPU (`check_hist_args`).
+    ``out`` / ``skipped`` (contiguous int32 of those shapes on the device) receive the result; default new tensors.  The counters are
+    unsigned 32-bit; torch has no arithmetic for that type, so they are handed out as int32 (a segment has fewer than 2^31 frames).
+    See ``jamun_hist2d_pairs``."""
+    if not torch.is_tensor(angles) or angles.ndim != 2:
+        raise ValueError(f"angles must be a [frames, width] tensor, got {tuple(getattr(angles, 'shape', ()))}")
+    T, W = int(angles.shape[0]), int(angles.shape[1])
+    on_device = torch.is_tensor(pairs) and pairs.is_cuda
+    host_pairs, bins, cuts = check_hist_args(T, W, None if on_device else pairs, bins, cuts)
+    if not angles.is_cuda or angles.dtype != torch.float32 or (W > 1 and angles.stride(1) != 1) or (T > 1 and angles.stride(0) < W):
+        raise RuntimeError(f"angles must be a float32 tensor on the GPU with adjacent columns, got {angles.dtype} {tuple(angles.shape)} "
+                           f"strides {tuple(angles.stride())} on {angles.device}")
+    lib = _lib.load()
+    dev = angles.device
+    if on_device:
+        if pairs.device != dev or pairs.dtype != torch.int32 or pairs.ndim != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+            raise ValueError(f"a pairs table on the device must be a contiguous int32 [P, 2] tensor on {dev}, got {pairs.dtype} "
+                             f"{tuple(pairs.shape)} on {pairs.device}")
+    else:
+        pairs = torch.from_numpy(host_pairs).to(dev)
+    P, C = int(pairs.shape[0]), int(cuts.shape[0])
+    key = (str(dev), bins)
+    if key not in _hist_edges:
+        _hist_edges[key] = torch.from_numpy(hist_edges(bins)).to(dev)
+    edges = _hist_edges[key]
+    if out is None:
+        out = torch.empty((C, P, bins, bins), dtype=torch.int32, device=dev)
+    elif out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != (C, P, bins, bins) or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous int32 [{C}, {P}, {bins}, {bins}] tensor on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if skipped is None:
+        skipped = torch.empty((C, P), dtype=torch.int32, device=dev)
+    elif skipped.device != dev or skipped.dtype != torch.int32 or tuple(skipped.shape) != (C, P) or not skipped.is_contiguous():
+        raise RuntimeError(f"skipped must be a contiguous int32 [{C}, {P}] tensor on {dev}, got {skipped.dtype} {tuple(skipped.shape)} on {skipped.device}")
+    row_stride = int(angles.stride(0)) if T > 1 else W
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_hist2d_pairs(_ptr(angles), row_stride, T, W, _ptr(pairs), P, _ptr(edges), bins, cuts.ctypes.data, C, _ptr(out), int(out.numel()), _ptr(skipped), _stream()))
+    return out, skipped
+
+
+def js_divergence(counts: torch.Tensor, ref_counts: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Queue the Jensen-Shannon divergences of the prefix sums of the segment histograms ``counts [C, P, B, B]`` (int32 on the device, as
+    `hist2d_pairs` returns them) against ``ref_counts [P, B, B]`` or ``[B, B]`` (int32, same device): ``(pooled float64 [C], per_pair
+    float64 [C, P])`` in nats, as `ramachandran.js_divergence_host` defines them.  A prefix or a reference without a count gives NaN
+    (the host specification raises for an empty reference; nothing is read back here).  See ``jamun_js_divergence``."""
+    if not torch.is_tensor(counts) or counts.ndim != 4 or counts.shape[2] != counts.shape[3] or counts.dtype != torch.int32:
+        raise ValueError(f"counts must be an int32 [C, P, B, B] tensor, got {getattr(counts, 'dtype', None)} {tuple(getattr(counts, 'shape', ()))}")
+    C, P, B = int(counts.shape[0]), int(counts.shape[1]), int(counts.shape[2])
+    if not torch.is_tensor(ref_counts) or ref_counts.dtype != torch.int32 or tuple(ref_counts.shape) not in ((P, B, B), (B, B)):
+        raise ValueError(f"ref_counts must be an int32 [{P}, {B}, {B}] or [{B}, {B}] tensor, got {getattr(ref_counts, 'dtype', None)} "
+                         f"{tuple(getattr(ref_counts, 'shape', ()))}")
+    if not 1 <= B <= HIST_MAX_BINS or not 1 <= C <= HIST_MAX_CUTS or P < 1:
+        raise ValueError(f"{C} cuts, {P} pairs, {B} bins: at most {HIST_MAX_CUTS} cuts and {HIST_MAX_BINS} bins, and at least one of each")
+    if not counts.is_cuda or ref_counts.device != counts.device or not counts.is_contiguous() or not ref_counts.is_contiguous():
+        raise RuntimeError(f"counts and ref_counts must be contiguous tensors on one GPU, got {counts.device} and {ref_counts.device}")
+    lib = _lib.load()
+    pooled = torch.empty((C,), dtype=torch.float64, device=counts.device)
+    per_pair = torch.empty((C, P), dtype=torch.float64, device=counts.device)
+    with torch.cuda.device(counts.device):
+        _lib.check(lib.jamun_js_divergence(_ptr(counts), C, P, B, _ptr(ref_counts), P if ref_counts.ndim == 3 else 1, _ptr(pooled),
+                                           _ptr(per_pair), _stream()))
+    return pooled, per_pair
