@@ -312,6 +312,26 @@ int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_fr
 int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pairs, int32_t bins, const uint32_t* ref_dev, int32_t n_ref_pairs,
                         double* pooled_dev, double* per_pair_dev, void* stream);
 
+/* ---- chemical validity: clashing non-bonded pairs and bonds of a wrong length, per frame ---------------------------------------------------
+ * What the reference's metrics/_chemical_validity.py counts (_check_volume_exclusion, _check_bond_lengths), for every frame, on the device.
+ * Frames are addressed as the encoders above address them (frame and atom strides in floats, components adjacent); 1 <= n_atoms <= 256.
+ * For a pair (i, j) the number compared is s = (dx dx + dy dy) + dz dz, dx = x_j - x_i, every operation in fp32 in this order:
+ *   clash_s_dev   fp32 [n_atoms (n_atoms - 1) / 2]  one threshold per pair i < j, the upper triangle in row-major order; the pair clashes when
+ *                                                   s < clash_s.  A bonded pair carries 0.  May be NULL when n_atoms == 1.
+ *   bonds_dev     int32 [n_bonds][2]                the bonds; bond b is off when s < bond_lo_s_dev[b] or s > bond_hi_s_dev[b] (fp32 [n_bonds]).
+ *                                                   A row with an index outside [0, n_atoms) is skipped and reads nothing.  All three may be
+ *                                                   NULL when n_bonds == 0.
+ *   counts_dev    uint32 [n_frames][2]              (clashes, bonds that are off) of every frame; written whole by the call.
+ *   bond_frames_dev uint32 [n_bonds] or NULL        the number of frames in which bond b is off; zeroed by the call (on `stream`).
+ * The thresholds are made on the host so that the comparisons are those of the reference on fl32(sqrt(s)) (jamun_amd/validity.py); the
+ * kernel takes no square root and the counts equal a host's that does the same fp32 operations, integer for integer.  A NaN compares false:
+ * no issue; s = +inf is a bond that is off and no clash.  n_atoms == 1 gives zeros.  n_atoms outside [1, 256], a negative count or stride,
+ * counts_capacity (in counters) below 2 n_frames or a NULL pointer that is needed is JAMUN_ERR_INVALID and nothing is written;
+ * n_frames == 0 launches nothing and succeeds.  Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation. */
+int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames,
+                          const float* clash_s_dev, const int32_t* bonds_dev, const float* bond_lo_s_dev, const float* bond_hi_s_dev,
+                          int32_t n_bonds, uint32_t* counts_dev, int64_t counts_capacity, uint32_t* bond_frames_dev, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

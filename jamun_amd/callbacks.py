@@ -533,6 +533,21 @@ class RamachandranMetricsCallback(TrajectoryMetricCallback):
         super().__init__(datasets, functools.partial(RamachandranMetrics, **kw))
 
 
+class ChemicalValidityMetricsCallback(TrajectoryMetricCallback):
+    """`TrajectoryMetricCallback` over `validity.ChemicalValidityMetrics` (the reference's ``ChemicalValidityMetricsCallback``,
+    ``callbacks/sampler/chemical_validity.yaml``, without its wandb histograms): per checked frame the share of clashing non-bonded pairs
+    and of bonds of a wrong length, under ``<output_dir>/<label>/chemical_validity/``.  Keyword arguments go to the meter
+    (``volume_exclusion_tolerance``, ``bond_length_tolerance``, ``num_molecules_per_trajectory``, ``sample_key``, ``output_dir``,
+    ``device``, ``vdw_radii``, ``covalent_radii``)."""
+
+    def __init__(self, datasets: Sequence, **kw):
+        import functools
+
+        from .validity import ChemicalValidityMetrics
+
+        super().__init__(datasets, functools.partial(ChemicalValidityMetrics, **kw))
+
+
 class MeasureSamplingTimeCallback:
     """Wall time per batch and per sampled conformation (one saved (walker, frame) pair — the reference's unit,
     ``callbacks/sampler/_measure_sampling_time.py:57,71``).  Writes ``sampler/timing.json`` on rank 0."""

@@ -36,6 +36,7 @@ TARGET_ALIASES = {
     "jamun.callbacks.sampler.MeasureSamplingTimeCallback": "jamun_amd.callbacks.MeasureSamplingTimeCallback",
     "jamun.callbacks.sampler.TrajectoryMetricCallback": "jamun_amd.callbacks.TrajectoryMetricCallback",
     "jamun.callbacks.sampler.RamachandranPlotMetricsCallback": "jamun_amd.callbacks.RamachandranMetricsCallback",
+    "jamun.callbacks.sampler.ChemicalValidityMetricsCallback": "jamun_amd.callbacks.ChemicalValidityMetricsCallback",
     "jamun.sampling.walkjump.MeasurementDependentParametersCallback": "jamun_amd.sampling.MeasurementDependentParametersCallback",
     "jamun.sampling.walkjump.InterpolateParametersCallback": "jamun_amd.sampling.InterpolateParametersCallback",
     "jamun.utils.ModelSamplingWrapper": "jamun_amd.sampling.ModelSamplingWrapper",

@@ -1195,6 +1195,29 @@ int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pa
   });
 }
 
+// ---- chemical validity of frames (jamun_validity.hip) --------------------------------------------------------------------------------------
+
+int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* clash_s_dev,
+                          const int32_t* bonds_dev, const float* bond_lo_s_dev, const float* bond_hi_s_dev, int32_t n_bonds, uint32_t* counts_dev,
+                          int64_t counts_capacity, uint32_t* bond_frames_dev, void* stream) {
+  return guarded([&] {
+    if (frame_stride < 0 || atom_stride < 0 || n_frames < 0 || n_bonds < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (n_atoms < 1 || n_atoms > JAMUN_VALIDITY_MAX_ATOMS)
+      throw Err(JAMUN_ERR_INVALID, "n_atoms " + std::to_string(n_atoms) + " is outside [1, " + std::to_string(JAMUN_VALIDITY_MAX_ATOMS) + "]");
+    const int64_t need = 2 * (int64_t)n_frames;
+    if (counts_capacity < need)
+      throw Err(JAMUN_ERR_INVALID, "counts_capacity " + std::to_string(counts_capacity) + " is too small: the frames need " + std::to_string(need) + " counters");
+    if (n_frames == 0) return;  // (nothing to write)
+    if (!xyz_dev || !counts_dev || (n_atoms > 1 && !clash_s_dev) || (n_bonds > 0 && (!bonds_dev || !bond_lo_s_dev || !bond_hi_s_dev)))
+      throw Err(JAMUN_ERR_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (bond_frames_dev && n_bonds > 0) HIPCHECK(hipMemsetAsync(bond_frames_dev, 0, (size_t)n_bonds * sizeof(uint32_t), st));
+    launch_validity_frames(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, clash_s_dev, bonds_dev, bond_lo_s_dev, bond_hi_s_dev, n_bonds,
+                           counts_dev, bond_frames_dev, st);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
 int jamun_build_edges(jamun_sampler* s, const float* y_dev, void* stream) {
   return guarded([&] {
     if (!s || !y_dev) throw Err(JAMUN_ERR_INVALID, "null argument");

@@ -526,3 +526,10 @@ void launch_hist2d_pairs(const float* angles, long long row_stride, int width, c
                          const JamunHistCuts& cuts, unsigned* counts, unsigned* skipped, hipStream_t st);
 void launch_js_divergence(const unsigned* counts, int n_cuts, int n_pairs, int bins, const unsigned* ref, int n_ref_pairs, double* pooled,
                           double* per_pair, hipStream_t st);
+// jamun_validity.hip — per frame the clashing non-bonded pairs and the bonds of a wrong length, from thresholds on the SQUARED distance; n_frames >= 1
+#define JAMUN_VALIDITY_MAX_ATOMS 256    // atoms the device path takes (native.VALIDITY_MAX_ATOMS mirrors it): 32 640 pair thresholds
+#define JAMUN_VALIDITY_CHUNK 64         // atoms whose positions a workgroup stages in LDS at a time: 48 KB (native.VALIDITY_CHUNK, for the tests)
+#define JAMUN_VALIDITY_SPLIT_ATOMS 32   // above this many atoms four waves share a workgroup's 64 frames (native.VALIDITY_SPLIT_ATOMS)
+void launch_validity_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* clash_s,
+                            const int* bonds, const float* bond_lo_s, const float* bond_hi_s, int n_bonds, unsigned* counts,
+                            unsigned* bond_frames, hipStream_t st);

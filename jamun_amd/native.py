@@ -714,3 +714,103 @@ def js_divergence(counts: torch.Tensor, ref_counts: torch.Tensor) -> Tuple[torch
         _lib.check(lib.jamun_js_divergence(_ptr(counts), C, P, B, _ptr(ref_counts), P if ref_counts.ndim == 3 else 1, _ptr(pooled),
                                            _ptr(per_pair), _stream()))
     return pooled, per_pair
+
+
+# ---- chemical validity of frames (jamun_validity.hip) -----------------------------------------------------------------------------------------
+
+VALIDITY_MAX_ATOMS = 256    # atoms k_validity_frames takes (JAMUN_VALIDITY_MAX_ATOMS, jamun_internal.h)
+VALIDITY_CHUNK = 64         # atoms a workgroup stages in LDS at a time (JAMUN_VALIDITY_CHUNK)
+VALIDITY_SPLIT_ATOMS = 32   # above this many atoms four waves share a workgroup's frames (JAMUN_VALIDITY_SPLIT_ATOMS)
+
+_VALIDITY_KEYS = (("clash_s", np.float32), ("bonds", np.int32), ("bond_lo_s", np.float32), ("bond_hi_s", np.float32))
+
+
+def check_validity_tables(tables, n_atoms: int) -> Dict[str, np.ndarray]:
+    """The tables of `validity_counts` (``clash_s`` float32 ``[n (n - 1) / 2]``, ``bonds`` integer ``[B, 2]``, ``bond_lo_s`` / ``bond_hi_s``
+    float32 ``[B]``: what `validity.validity_tables` makes) checked on the host; ``ValueError`` for a wrong type or shape, a bond with an
+    index outside ``[0, n_atoms)`` or a bond of an atom with itself.  Returns the four as contiguous arrays (float32 / int32)."""
+    out = {}
+    for key, dtype in _VALIDITY_KEYS:
+        a = tables[key]
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        kind = "iu" if dtype is np.int32 else "f"
+        if a.dtype.kind not in kind or (kind == "f" and a.dtype != np.float32):
+            raise ValueError(f"{key} must hold {'integers' if kind == 'iu' else 'float32'}, got {a.dtype}")
+        out[key] = a
+    pairs = n_atoms * (n_atoms - 1) // 2
+    if out["clash_s"].shape != (pairs,):
+        raise ValueError(f"clash_s must have shape [{pairs}] for {n_atoms} atoms, got {tuple(out['clash_s'].shape)}")
+    b = out["bonds"].reshape(-1, 2) if out["bonds"].size == 0 else out["bonds"]
+    if b.ndim != 2 or b.shape[1] != 2:
+        raise ValueError(f"bonds must have shape [B, 2], got {tuple(b.shape)}")
+    b = b.astype(np.int64)
+    bad = ((b < 0) | (b >= n_atoms)).any(axis=1) | (b[:, 0] == b[:, 1])
+    if bad.any():
+        j = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"bond {j}, {b[j].tolist()}, is not two different atoms in [0, {n_atoms})")
+    B = int(b.shape[0])
+    for key in ("bond_lo_s", "bond_hi_s"):
+        if out[key].shape != (B,):
+            raise ValueError(f"{key} must have shape [{B}], got {tuple(out[key].shape)}")
+    out["bonds"] = b
+    return {key: np.ascontiguousarray(out[key], dtype=dtype) for key, dtype in _VALIDITY_KEYS}
+
+
+def upload_validity_tables(tables, n_atoms: int, device) -> Dict[str, torch.Tensor]:
+    """`check_validity_tables`, then the four tables as tensors on ``device``: upload once, call `validity_counts` often."""
+    return {key: torch.from_numpy(a).to(device) for key, a in check_validity_tables(tables, n_atoms).items()}
+
+
+def validity_counts(frames: torch.Tensor, tables, out: Optional[torch.Tensor] = None, bond_frames=None):
+    """Queue the chemical-validity counts of the frames ``frames [T, n, 3]`` (device fp32, a view of either trajectory layout, or any
+    strided selection of its frames) on the current stream: ``(counts int32 [T, 2], bond_frames int32 [B])``, per frame the clashing
+    non-bonded pairs and the bonds of a wrong length, per bond the frames in which it is off; `validity.validity_counts_host` is the
+    specification and the counts equal it integer for integer.  ``tables``: the dict of `validity.validity_tables` (or its four arrays
+    ``clash_s``, ``bonds``, ``bond_lo_s``, ``bond_hi_s``).  Host tables are checked (`check_validity_tables`) before anything needs a GPU
+    and uploaded; tables whose ``bonds`` is a tensor on the device of ``frames`` (`upload_validity_tables`) are taken as checked: the
+    kernel skips a bond with an index out of range, it never reads there.  ``out`` (contiguous int32 ``[T, 2]``) and ``bond_frames``
+    (contiguous int32 ``[B]``) receive the result; default new tensors; ``bond_frames=False`` asks for none and returns ``None`` for it.
+    The counters are unsigned 32-bit, handed out as int32 as `hist2d_pairs` hands out its own.  Nothing is read back.
+    See ``jamun_validity_counts``."""
+    if not torch.is_tensor(frames) or frames.ndim != 3 or frames.shape[2] != 3:
+        raise RuntimeError(f"frames must be a [frames, atoms, 3] tensor, got {tuple(getattr(frames, 'shape', ()))}")
+    n, T = int(frames.shape[1]), int(frames.shape[0])
+    if not 1 <= n <= VALIDITY_MAX_ATOMS:
+        raise ValueError(f"{n} atoms: the device path takes 1 to {VALIDITY_MAX_ATOMS} (validity.validity_counts_host has no limit)")
+    on_device = torch.is_tensor(tables["bonds"]) and tables["bonds"].is_cuda
+    if not on_device:
+        host = check_validity_tables(tables, n)  # (before anything needs a GPU)
+    fs, as_, _, _ = _frame_strides(frames)
+    if T > 0x7FFFFFFF:
+        raise RuntimeError(f"{T} frames: the count must fit 31 bits")
+    lib = _lib.load()
+    dev = frames.device
+    if on_device:
+        t = {key: tables[key] for key, _ in _VALIDITY_KEYS}
+        B = int(t["bonds"].shape[0])
+        want = {"clash_s": (torch.float32, (n * (n - 1) // 2,)), "bonds": (torch.int32, (B, 2)), "bond_lo_s": (torch.float32, (B,)),
+                "bond_hi_s": (torch.float32, (B,))}
+        for key, (dtype, shape) in want.items():
+            a = t[key]
+            if not torch.is_tensor(a) or a.device != dev or a.dtype != dtype or tuple(a.shape) != shape or not a.is_contiguous():
+                raise ValueError(f"{key} on the device must be a contiguous {dtype} {list(shape)} tensor on {dev}, got "
+                                 f"{getattr(a, 'dtype', None)} {tuple(getattr(a, 'shape', ()))} on {getattr(a, 'device', None)}")
+    else:
+        t = {key: torch.from_numpy(a).to(dev) for key, a in host.items()}
+        B = int(t["bonds"].shape[0])
+    if out is None:
+        out = torch.empty((T, 2), dtype=torch.int32, device=dev)
+    elif out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != (T, 2) or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous int32 [{T}, 2] tensor on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    if bond_frames is False:
+        bond_frames = None
+    elif bond_frames is None:
+        bond_frames = torch.zeros((B,), dtype=torch.int32, device=dev)  # (zeros: with T == 0 the call writes nothing)
+    elif bond_frames.device != dev or bond_frames.dtype != torch.int32 or tuple(bond_frames.shape) != (B,) or not bond_frames.is_contiguous():
+        raise RuntimeError(f"bond_frames must be a contiguous int32 [{B}] tensor on {dev}, got {bond_frames.dtype} {tuple(bond_frames.shape)} on {bond_frames.device}")
+    with torch.cuda.device(dev):
+        if T == 0 and bond_frames is not None:
+            bond_frames.zero_()
+        _lib.check(lib.jamun_validity_counts(_ptr(frames), fs, as_, n, T, _ptr(t["clash_s"]), _ptr(t["bonds"]), _ptr(t["bond_lo_s"]), _ptr(t["bond_hi_s"]),
+                                             B, _ptr(out), int(out.numel()), _ptr(bond_frames), _stream()))
+    return out, bond_frames
