@@ -203,6 +203,15 @@ def load() -> C.CDLL:
     return lib
 
 
+def available() -> bool:
+    """Whether the HIP library loads: what the callers that have a host path ask before they choose (`load` itself says why not)."""
+    try:
+        load()
+    except RuntimeError:
+        return False
+    return True
+
+
 def check(code: int) -> None:
     if code != 0:
         msg = load().jamun_last_error()

@@ -259,13 +259,9 @@ class SaveTrajectoryCallback:
             return True
         if not on_gpu or grouped:
             return False
-        try:
-            from . import _lib
+        from . import _lib
 
-            _lib.load()
-        except RuntimeError:
-            return False
-        return True
+        return _lib.available()
 
     def on_after_sample_batch(self, sample: Sequence[dict], sampler):
         error = self._finished_writer_error()

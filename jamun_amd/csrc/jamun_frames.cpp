@@ -1,0 +1,198 @@
+// jamun_frames.cpp — the C entries that encode or analyse frames of a trajectory and never touch a jamun_sampler: the PDB / DCD encoders
+// (jamun_traj.hip), superposition (jamun_superpose.hip), internal coordinates (jamun_intcoord.hip), histograms of angle pairs with their
+// Jensen-Shannon divergence (jamun_hist.hip) and chemical validity (jamun_validity.hip).  Every refusal is raised before any HIP call.
+// The order of an entry's checks decides which message a caller with two faults sees, and the entries differ in it on purpose: where a
+// shared check below would change an order or a text, the entry keeps a line of its own.  Every entry's checks read top to bottom.
+#include "jamun_host.h"
+
+namespace {
+
+// A [n_frames, n_atoms, 3] view of floats: any strides over frames and atoms, the three components adjacent
+struct FramesView {
+  const float* ptr;
+  int64_t frame_stride, atom_stride;
+  int32_t n_atoms, n_frames;
+  bool negative() const { return frame_stride < 0 || atom_stride < 0 || n_atoms < 0 || n_frames < 0; }  // (a stride or a count)
+  // floats spanned: one past the last component (n_frames, n_atoms >= 1)
+  unsigned __int128 span() const {
+    return (unsigned __int128)(n_frames - 1) * (unsigned __int128)frame_stride + (unsigned __int128)(n_atoms - 1) * (unsigned __int128)atom_stride + 3;
+  }
+};
+
+void require_capacity(const char* name, int64_t have, int64_t need, const char* what, const char* unit) {
+  if (have < need)
+    throw Err(JAMUN_ERR_INVALID, std::string(name) + " " + std::to_string(have) + " is too small: the " + what + " need " + std::to_string(need) + " " + unit);
+}
+
+void check_bins(int32_t bins) {
+  if (bins < 1 || bins > JAMUN_HIST_MAX_BINS)
+    throw Err(JAMUN_ERR_INVALID, "bins " + std::to_string(bins) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_BINS) + "]");
+}
+
+void check_n_cuts(int32_t n_cuts) {
+  if (n_cuts < 1 || n_cuts > JAMUN_HIST_MAX_CUTS)
+    throw Err(JAMUN_ERR_INVALID, "n_cuts " + std::to_string(n_cuts) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_CUTS) + "]");
+}
+
+constexpr int64_t kMaxModel = 1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
+
+int64_t checked_pdb_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames) {
+  if (body_len < 0 || first_model < 0 || n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+  if (body_len > INT32_MAX) throw Err(JAMUN_ERR_INVALID, "body_len must fit 31 bits");
+  if (first_model > kMaxModel || n_frames > kMaxModel) throw Err(JAMUN_ERR_INVALID, "model numbers must stay below 10^15");
+  return pdb_models_nbytes(body_len, first_model, n_frames);
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- trajectory file encoders (jamun_traj.hip) ----------------------------------------------------------------------------------------
+
+int jamun_pdb_models_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames, int64_t* nbytes) {
+  return guarded([&] {
+    if (!nbytes) throw Err(JAMUN_ERR_INVALID, "null argument");
+    *nbytes = checked_pdb_nbytes(body_len, first_model, n_frames);
+  });
+}
+
+int jamun_encode_pdb_models(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, int64_t first_model,
+                            const uint8_t* body_dev, int64_t body_len, const int32_t* coord_off_dev, uint8_t* out_dev, int64_t out_capacity,
+                            uint32_t* unencodable_dev, void* stream) {
+  return guarded([&] {
+    const FramesView in{xyz_dev, frame_stride, atom_stride, n_atoms, n_frames};
+    if (!in.ptr || !body_dev || !coord_off_dev || !out_dev || !unencodable_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (in.negative() || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if ((int64_t)n_atoms + 1 > 99999) throw Err(JAMUN_ERR_INVALID, "n_atoms + 1 > 99999: the serial field of the ATOM / TER records would widen");
+    const int64_t need = checked_pdb_nbytes(body_len, first_model, n_frames);
+    require_capacity("out_capacity", out_capacity, need, "models", "bytes");
+    if (n_frames == 0) return;
+    launch_encode_pdb(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, first_model, body_dev, (int)body_len, coord_off_dev, out_dev,
+                      unencodable_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_encode_dcd_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, uint8_t* out_dev,
+                            int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    const FramesView in{xyz_dev, frame_stride, atom_stride, n_atoms, n_frames};
+    if (!in.ptr || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (in.negative() || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (reinterpret_cast<uintptr_t>(out_dev) & 3) throw Err(JAMUN_ERR_INVALID, "out_dev must be 4-byte aligned");
+    const int64_t need = (int64_t)n_frames * 3 * (4 * (int64_t)n_atoms + 8);
+    require_capacity("out_capacity", out_capacity, need, "frames", "bytes");
+    if (n_frames == 0) return;
+    launch_encode_dcd(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- superposition (jamun_superpose.hip) -------------------------------------------------------------------------------------------------
+
+int jamun_superpose_frames(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* ref_dev,
+                           float* out_dev, int64_t out_frame_stride, int64_t out_atom_stride, float* rmsd_dev, void* stream) {
+  return guarded([&] {
+    const FramesView in{xyz_dev, frame_stride, atom_stride, n_atoms, n_frames}, out{out_dev, out_frame_stride, out_atom_stride, n_atoms, n_frames};
+    if (!in.ptr || !ref_dev || !out.ptr) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (in.negative() || out.negative()) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (n_frames == 0 || n_atoms == 0) return;  // (no frame, or frames without atoms: nothing to write, no RMSD to define)
+    const bool in_place = out_dev == xyz_dev && out_frame_stride == frame_stride && out_atom_stride == atom_stride;
+    if (!in_place) {
+      const unsigned __int128 a0 = reinterpret_cast<uintptr_t>(xyz_dev), b0 = reinterpret_cast<uintptr_t>(out_dev);
+      const unsigned __int128 a1 = a0 + 4 * in.span();
+      const unsigned __int128 b1 = b0 + 4 * out.span();
+      if (a0 < b1 && b0 < a1)
+        throw Err(JAMUN_ERR_INVALID, "out_dev overlaps xyz_dev: the output may be the input itself with the same strides (in place), or memory apart from it");
+    }
+    launch_superpose_frames(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, ref_dev, out_dev, out_frame_stride, out_atom_stride, rmsd_dev,
+                            (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- internal coordinates (jamun_intcoord.hip) ---------------------------------------------------------------------------------------------
+
+int jamun_internal_coords(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const int32_t* idx_dev,
+                          int32_t n_feat, int32_t cossin, float* out_dev, int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    const FramesView in{xyz_dev, frame_stride, atom_stride, n_atoms, n_frames};
+    if (in.negative() || n_feat < 0 || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    const int64_t need = (int64_t)n_frames * (int64_t)n_feat * (cossin ? 2 : 1);  // (< 2^63: two 31-bit counts and a factor 2)
+    require_capacity("out_capacity", out_capacity, need, "features", "floats");
+    if (n_frames == 0 || n_feat == 0) return;  // (nothing to write)
+    if (!in.ptr || !idx_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");  // (after the empty return: an empty call may pass null)
+    launch_internal_coords(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, idx_dev, n_feat, cossin != 0, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- histograms of angle pairs and their Jensen-Shannon divergence (jamun_hist.hip) --------------------------------------------------------
+
+int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_frames, int32_t width, const int32_t* pairs_dev, int32_t n_pairs,
+                       const double* edges_dev, int32_t bins, const int32_t* cuts, int32_t n_cuts, uint32_t* counts_dev,
+                       int64_t counts_capacity, uint32_t* skipped_dev, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0 || width < 0 || n_pairs < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_bins(bins);
+    check_n_cuts(n_cuts);
+    if (!cuts) throw Err(JAMUN_ERR_INVALID, "null argument");
+    JamunHistCuts k;
+    k.n = n_cuts;
+    for (int c = 0; c < JAMUN_HIST_MAX_CUTS; ++c) k.cut[c] = c < n_cuts ? cuts[c] : 0;
+    for (int c = 0; c < n_cuts; ++c)
+      if (k.cut[c] < 1 || k.cut[c] > n_frames || (c > 0 && k.cut[c] <= k.cut[c - 1]))
+        throw Err(JAMUN_ERR_INVALID, "cuts[" + std::to_string(c) + "] = " + std::to_string(k.cut[c]) + ": the cuts must ascend strictly within [1, " +
+                                         std::to_string(n_frames) + "]");
+    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    if (n_pairs > 65535) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is above 65535");
+    const int64_t need = (int64_t)n_cuts * (int64_t)n_pairs * bins * bins;  // (< 2^37)
+    require_capacity("counts_capacity", counts_capacity, need, "histograms", "counters");
+    if (n_pairs == 0) return;  // (nothing to write)
+    if (!angles_dev || !pairs_dev || !edges_dev || !counts_dev || !skipped_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHECK(hipMemsetAsync(counts_dev, 0, (size_t)need * sizeof(uint32_t), st));
+    HIPCHECK(hipMemsetAsync(skipped_dev, 0, (size_t)n_cuts * n_pairs * sizeof(uint32_t), st));
+    launch_hist2d_pairs(angles_dev, row_stride, width, pairs_dev, n_pairs, edges_dev, bins, k, counts_dev, skipped_dev, st);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pairs, int32_t bins, const uint32_t* ref_dev, int32_t n_ref_pairs,
+                        double* pooled_dev, double* per_pair_dev, void* stream) {
+  return guarded([&] {
+    check_bins(bins);
+    check_n_cuts(n_cuts);
+    if (n_pairs < 1 || n_pairs > 65534) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is outside [1, 65534]");
+    if (n_ref_pairs != 1 && n_ref_pairs != n_pairs)
+      throw Err(JAMUN_ERR_INVALID, "n_ref_pairs " + std::to_string(n_ref_pairs) + " is neither 1 nor n_pairs = " + std::to_string(n_pairs));
+    if (!counts_dev || !ref_dev || !pooled_dev || !per_pair_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_js_divergence(counts_dev, n_cuts, n_pairs, bins, ref_dev, n_ref_pairs, pooled_dev, per_pair_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- chemical validity of frames (jamun_validity.hip) --------------------------------------------------------------------------------------
+
+int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t atom_stride, int32_t n_atoms, int32_t n_frames, const float* clash_s_dev,
+                          const int32_t* bonds_dev, const float* bond_lo_s_dev, const float* bond_hi_s_dev, int32_t n_bonds, uint32_t* counts_dev,
+                          int64_t counts_capacity, uint32_t* bond_frames_dev, void* stream) {
+  return guarded([&] {
+    // (not FramesView::negative: a negative n_atoms is answered with its range below)
+    if (frame_stride < 0 || atom_stride < 0 || n_frames < 0 || n_bonds < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    if (n_atoms < 1 || n_atoms > JAMUN_VALIDITY_MAX_ATOMS)
+      throw Err(JAMUN_ERR_INVALID, "n_atoms " + std::to_string(n_atoms) + " is outside [1, " + std::to_string(JAMUN_VALIDITY_MAX_ATOMS) + "]");
+    const int64_t need = 2 * (int64_t)n_frames;
+    require_capacity("counts_capacity", counts_capacity, need, "frames", "counters");
+    if (n_frames == 0) return;  // (nothing to write)
+    if (!xyz_dev || !counts_dev || (n_atoms > 1 && !clash_s_dev) || (n_bonds > 0 && (!bonds_dev || !bond_lo_s_dev || !bond_hi_s_dev)))
+      throw Err(JAMUN_ERR_INVALID, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    if (bond_frames_dev && n_bonds > 0) HIPCHECK(hipMemsetAsync(bond_frames_dev, 0, (size_t)n_bonds * sizeof(uint32_t), st));
+    launch_validity_frames(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, clash_s_dev, bonds_dev, bond_lo_s_dev, bond_hi_s_dev, n_bonds,
+                           counts_dev, bond_frames_dev, st);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+}  // extern "C"

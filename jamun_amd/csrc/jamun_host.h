@@ -1,5 +1,6 @@
 // jamun_host.h — host-only declarations shared by jamun_pack.cpp (weight packing), jamun_plan.cpp (tile / work-list planning and
-// kernel selection) and jamun_api.cpp (sampler create, dispatch, the C ABI).  Not included by any .hip file.
+// kernel selection), jamun_api.cpp (sampler create, dispatch, the C ABI) and jamun_frames.cpp (the C entries on frames).  Not included
+// by any .hip file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,24 @@ struct Err : std::runtime_error {
     hipError_t _e = (expr);                                                                            \
     if (_e != hipSuccess) throw Err(JAMUN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+
+// The calling thread's last error (jamun_last_error) and the wrapper every C entry runs its body in: an exception becomes its code and
+// leaves its text in the slot.  One definition for every host file; the library does not export it.
+__attribute__((visibility("hidden"))) inline thread_local std::string jamun_error_slot;
+
+template <typename F>
+int guarded(F&& f) {
+  try {
+    f();
+    return JAMUN_OK;
+  } catch (const Err& e) {
+    jamun_error_slot = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    jamun_error_slot = e.what();
+    return JAMUN_ERR_INVALID;
+  }
+}
 
 // Owner of device (and pinned host) memory: every allocation it hands out is recorded and freed by clear() / the destructor, so a throw
 // anywhere in sampler create gives back what was uploaded so far.  Structs keep plain T* fields into it.  live_allocs / live_bytes count

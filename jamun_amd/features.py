@@ -100,13 +100,9 @@ def internal_coords(frames, index, cossin: bool = False):
     to the HIP kernel (float32 out, no copy of a strided chain view) when the native library loads; everything else goes through
     `internal_coords_host` (float64 out).  Tensors in, tensors out (on the device of ``frames``); arrays in, arrays out."""
     if torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.float32:
-        try:
-            from . import _lib, native
+        from . import _lib, native
 
-            _lib.load()
-        except RuntimeError:
-            native = None
-        if native is not None:
+        if _lib.available():
             return native.internal_coords(frames, index, cossin=cossin)
     out = internal_coords_host(frames, index, cossin=cossin)
     return torch.from_numpy(out).to(frames.device) if torch.is_tensor(frames) else out

@@ -508,6 +508,42 @@ def encode_dcd_frames(xyz: torch.Tensor, out: torch.Tensor) -> int:
     return T * 3 * (4 * n + 8)
 
 
+# ---- what the analysis calls below share ------------------------------------------------------------------------------------------------
+
+def _result(name: str, given: Optional[torch.Tensor], shape: tuple, dtype: torch.dtype, device, fill=None) -> torch.Tensor:
+    """The tensor a result is written to: ``given`` if it is a contiguous ``dtype`` tensor of ``shape`` on ``device`` (``RuntimeError``
+    otherwise), else a new one, holding ``fill`` where the call may write nothing."""
+    if given is None:
+        return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
+    if given.device != device or given.dtype != dtype or tuple(given.shape) != tuple(shape) or not given.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on {device}, "
+                           f"got {given.dtype} {tuple(given.shape)} on {given.device}")
+    return given
+
+
+def _on_device(table) -> bool:
+    return torch.is_tensor(table) and table.is_cuda
+
+
+def _table(what: str, spec: str, table, on_device: bool, device, dtype: torch.dtype, shape: tuple) -> torch.Tensor:
+    """A table of indices or thresholds as a tensor on ``device``.  A host table (an array its ``check_*`` function returned) is uploaded;
+    one handed in on the device is taken as checked once it is a contiguous ``dtype`` tensor of ``shape`` there (``None``: any length),
+    ``ValueError`` otherwise.  ``spec`` is how the message words type and shape."""
+    if not on_device:
+        return torch.from_numpy(table).to(device)
+    if (not torch.is_tensor(table) or table.device != device or table.dtype != dtype or table.ndim != len(shape) or not table.is_contiguous()
+            or any(want is not None and want != have for want, have in zip(shape, table.shape))):
+        raise ValueError(f"{what} on the device must be a contiguous {spec} tensor on {device}, got {getattr(table, 'dtype', None)} "
+                         f"{tuple(getattr(table, 'shape', ()))} on {getattr(table, 'device', None)}")
+    return table
+
+
+def _fit_31_bits(text: str, *counts: int) -> None:
+    """``RuntimeError(text)`` if one of ``counts`` is more than the C entries' int32 arguments hold."""
+    if any(c > 0x7FFFFFFF for c in counts):
+        raise RuntimeError(text)
+
+
 # ---- superposition (jamun_superpose.hip) ----------------------------------------------------------------------------------------------
 
 def superpose_frames(frames: torch.Tensor, ref: torch.Tensor, out: Optional[torch.Tensor] = None, rmsd: Optional[torch.Tensor] = None,
@@ -519,14 +555,13 @@ def superpose_frames(frames: torch.Tensor, ref: torch.Tensor, out: Optional[torc
     buffer and returns ``None`` for it.  See ``jamun_superpose_frames``."""
     lib = _lib.load()
     fs, as_, n, T = _frame_strides(frames)
-    if n > 0x7FFFFFFF or T > 0x7FFFFFFF:
-        raise RuntimeError(f"{T} frames of {n} atoms: both counts must fit 31 bits")
+    _fit_31_bits(f"{T} frames of {n} atoms: both counts must fit 31 bits", n, T)
     if not ref.is_cuda or ref.device != frames.device or ref.dtype != torch.float32 or tuple(ref.shape) != (n, 3):
         raise RuntimeError(f"ref must be a float32 [{n}, 3] tensor on {frames.device}, got {ref.dtype} {tuple(ref.shape)} on {ref.device}")
     ref = ref.contiguous()
     if out is None:
         out = torch.empty_like(frames)  # (keeps the strides of a dense view such as a transposed chain)
-    if out.device != frames.device or tuple(out.shape) != tuple(frames.shape):
+    if out.device != frames.device or tuple(out.shape) != tuple(frames.shape):  # (a strided view: not `_result`'s contiguous tensor)
         raise RuntimeError(f"out must be a [{T}, {n}, 3] tensor on {frames.device}, got {tuple(out.shape)} on {out.device}")
     ofs, oas, _, _ = _frame_strides(out)
     if not want_rmsd:
@@ -534,7 +569,7 @@ def superpose_frames(frames: torch.Tensor, ref: torch.Tensor, out: Optional[torc
     elif rmsd is None:
         rmsd = torch.empty(T, dtype=torch.float32, device=frames.device)
     elif rmsd.device != frames.device or rmsd.dtype != torch.float32 or tuple(rmsd.shape) != (T,) or not rmsd.is_contiguous():
-        raise RuntimeError(f"rmsd must be a contiguous float32 [{T}] tensor on {frames.device}")
+        raise RuntimeError(f"rmsd must be a contiguous float32 [{T}] tensor on {frames.device}")  # (its own text: no "got")
     with torch.cuda.device(frames.device):
         if rmsd is not None and n == 0:
             rmsd.zero_()  # (frames without atoms: the call writes nothing)
@@ -580,25 +615,16 @@ def internal_coords(frames: torch.Tensor, index, cossin: bool = False, out: Opti
     the device) receives the result; default a new tensor.  See ``jamun_internal_coords``."""
     if not torch.is_tensor(frames) or frames.ndim != 3 or frames.shape[2] != 3:
         raise RuntimeError(f"frames must be a [frames, atoms, 3] tensor, got {tuple(getattr(frames, 'shape', ()))}")
-    on_device = torch.is_tensor(index) and index.is_cuda
+    on_device = _on_device(index)
     if not on_device:
         index = check_index_table(index, int(frames.shape[1]))  # (before anything needs a GPU)
     fs, as_, n, T = _frame_strides(frames)
-    if n > 0x7FFFFFFF or T > 0x7FFFFFFF or int(index.shape[0]) > 0x7FFFFFFF:
-        raise RuntimeError(f"{T} frames of {n} atoms, {int(index.shape[0])} features: the counts must fit 31 bits")
-    lib = _lib.load()
-    if on_device:
-        if index.device != frames.device or index.dtype != torch.int32 or index.ndim != 2 or index.shape[1] != 4 or not index.is_contiguous():
-            raise ValueError(f"an index table on the device must be a contiguous int32 [F, 4] tensor on {frames.device}, "
-                             f"got {index.dtype} {tuple(index.shape)} on {index.device}")
-    else:
-        index = torch.from_numpy(index).to(frames.device)
     F = int(index.shape[0])
+    _fit_31_bits(f"{T} frames of {n} atoms, {F} features: the counts must fit 31 bits", n, T, F)
+    lib = _lib.load()
+    index = _table("an index table", "int32 [F, 4]", index, on_device, frames.device, torch.int32, (None, 4))
     W = 2 * F if cossin else F
-    if out is None:
-        out = torch.empty((T, W), dtype=torch.float32, device=frames.device)
-    elif out.device != frames.device or out.dtype != torch.float32 or tuple(out.shape) != (T, W) or not out.is_contiguous():
-        raise RuntimeError(f"out must be a contiguous float32 [{T}, {W}] tensor on {frames.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+    out = _result("out", out, (T, W), torch.float32, frames.device)
     with torch.cuda.device(frames.device):
         _lib.check(lib.jamun_internal_coords(_ptr(frames), fs, as_, n, T, _ptr(index), F, 1 if cossin else 0, _ptr(out), int(out.numel()), _stream()))
     return out
@@ -616,6 +642,18 @@ _hist_edges: Dict[Tuple[str, int], torch.Tensor] = {}  # (device, bins) -> the u
 def hist_edges(bins: int) -> np.ndarray:
     """The bin edges of both axes, float64 ``[bins + 1]``: what ``np.histogram2d(..., bins, range=((-pi, pi), (-pi, pi)))`` uses."""
     return np.linspace(-np.pi, np.pi, int(bins) + 1)
+
+
+def check_cuts(cuts, n_frames: int) -> np.ndarray:
+    """The rule of the cuts, for `ramachandran.histogram_host` and `hist2d_pairs` alike: 1 to 64 integers ascending strictly within
+    ``[1, n_frames]`` (``ValueError`` otherwise), returned as int64.  Host only."""
+    c = np.asarray(cuts.detach().cpu().numpy() if torch.is_tensor(cuts) else cuts)
+    if c.ndim != 1 or c.dtype.kind not in "iu" or not 1 <= c.shape[0] <= HIST_MAX_CUTS:
+        raise ValueError(f"cuts must be 1 to {HIST_MAX_CUTS} integers, got {c.dtype} {tuple(c.shape)}")
+    c = c.astype(np.int64)
+    if c[0] < 1 or c[-1] > n_frames or (np.diff(c) <= 0).any():
+        raise ValueError(f"cuts must ascend strictly within [1, {n_frames}], got {c.tolist()}")
+    return c
 
 
 def check_hist_args(n_frames: int, width: int, pairs, bins, cuts) -> Tuple[Optional[np.ndarray], int, np.ndarray]:
@@ -638,13 +676,7 @@ def check_hist_args(n_frames: int, width: int, pairs, bins, cuts) -> Tuple[Optio
         pairs = np.ascontiguousarray(a, dtype=np.int32)
     if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= int(bins) <= HIST_MAX_BINS:
         raise ValueError(f"bins must be an integer in [1, {HIST_MAX_BINS}], got {bins!r}")
-    c = np.asarray(cuts.detach().cpu().numpy() if torch.is_tensor(cuts) else cuts)
-    if c.ndim != 1 or c.dtype.kind not in "iu" or not 1 <= c.shape[0] <= HIST_MAX_CUTS:
-        raise ValueError(f"cuts must be 1 to {HIST_MAX_CUTS} integers, got {c.dtype} {tuple(c.shape)}")
-    c = c.astype(np.int64)
-    if c[0] < 1 or c[-1] > n_frames or (np.diff(c) <= 0).any():
-        raise ValueError(f"cuts must ascend strictly within [1, {n_frames}], got {c.tolist()}")
-    return pairs, int(bins), np.ascontiguousarray(c, dtype=np.int32)
+    return pairs, int(bins), np.ascontiguousarray(check_cuts(cuts, n_frames), dtype=np.int32)
 
 
 def hist2d_pairs(angles: torch.Tensor, pairs, bins: int, cuts, out: Optional[torch.Tensor] = None,
@@ -660,32 +692,21 @@ def hist2d_pairs(angles: torch.Tensor, pairs, bins: int, cuts, out: Optional[tor
     if not torch.is_tensor(angles) or angles.ndim != 2:
         raise ValueError(f"angles must be a [frames, width] tensor, got {tuple(getattr(angles, 'shape', ()))}")
     T, W = int(angles.shape[0]), int(angles.shape[1])
-    on_device = torch.is_tensor(pairs) and pairs.is_cuda
+    on_device = _on_device(pairs)
     host_pairs, bins, cuts = check_hist_args(T, W, None if on_device else pairs, bins, cuts)
     if not angles.is_cuda or angles.dtype != torch.float32 or (W > 1 and angles.stride(1) != 1) or (T > 1 and angles.stride(0) < W):
         raise RuntimeError(f"angles must be a float32 tensor on the GPU with adjacent columns, got {angles.dtype} {tuple(angles.shape)} "
                            f"strides {tuple(angles.stride())} on {angles.device}")
     lib = _lib.load()
     dev = angles.device
-    if on_device:
-        if pairs.device != dev or pairs.dtype != torch.int32 or pairs.ndim != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
-            raise ValueError(f"a pairs table on the device must be a contiguous int32 [P, 2] tensor on {dev}, got {pairs.dtype} "
-                             f"{tuple(pairs.shape)} on {pairs.device}")
-    else:
-        pairs = torch.from_numpy(host_pairs).to(dev)
+    pairs = _table("a pairs table", "int32 [P, 2]", pairs if on_device else host_pairs, on_device, dev, torch.int32, (None, 2))
     P, C = int(pairs.shape[0]), int(cuts.shape[0])
     key = (str(dev), bins)
     if key not in _hist_edges:
         _hist_edges[key] = torch.from_numpy(hist_edges(bins)).to(dev)
     edges = _hist_edges[key]
-    if out is None:
-        out = torch.empty((C, P, bins, bins), dtype=torch.int32, device=dev)
-    elif out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != (C, P, bins, bins) or not out.is_contiguous():
-        raise RuntimeError(f"out must be a contiguous int32 [{C}, {P}, {bins}, {bins}] tensor on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if skipped is None:
-        skipped = torch.empty((C, P), dtype=torch.int32, device=dev)
-    elif skipped.device != dev or skipped.dtype != torch.int32 or tuple(skipped.shape) != (C, P) or not skipped.is_contiguous():
-        raise RuntimeError(f"skipped must be a contiguous int32 [{C}, {P}] tensor on {dev}, got {skipped.dtype} {tuple(skipped.shape)} on {skipped.device}")
+    out = _result("out", out, (C, P, bins, bins), torch.int32, dev)
+    skipped = _result("skipped", skipped, (C, P), torch.int32, dev)
     row_stride = int(angles.stride(0)) if T > 1 else W
     with torch.cuda.device(dev):
         _lib.check(lib.jamun_hist2d_pairs(_ptr(angles), row_stride, T, W, _ptr(pairs), P, _ptr(edges), bins, cuts.ctypes.data, C, _ptr(out), int(out.numel()), _ptr(skipped), _stream()))
@@ -777,37 +798,20 @@ def validity_counts(frames: torch.Tensor, tables, out: Optional[torch.Tensor] = 
     n, T = int(frames.shape[1]), int(frames.shape[0])
     if not 1 <= n <= VALIDITY_MAX_ATOMS:
         raise ValueError(f"{n} atoms: the device path takes 1 to {VALIDITY_MAX_ATOMS} (validity.validity_counts_host has no limit)")
-    on_device = torch.is_tensor(tables["bonds"]) and tables["bonds"].is_cuda
+    on_device = _on_device(tables["bonds"])
     if not on_device:
-        host = check_validity_tables(tables, n)  # (before anything needs a GPU)
+        tables = check_validity_tables(tables, n)  # (before anything needs a GPU)
     fs, as_, _, _ = _frame_strides(frames)
-    if T > 0x7FFFFFFF:
-        raise RuntimeError(f"{T} frames: the count must fit 31 bits")
+    _fit_31_bits(f"{T} frames: the count must fit 31 bits", T)
     lib = _lib.load()
     dev = frames.device
-    if on_device:
-        t = {key: tables[key] for key, _ in _VALIDITY_KEYS}
-        B = int(t["bonds"].shape[0])
-        want = {"clash_s": (torch.float32, (n * (n - 1) // 2,)), "bonds": (torch.int32, (B, 2)), "bond_lo_s": (torch.float32, (B,)),
-                "bond_hi_s": (torch.float32, (B,))}
-        for key, (dtype, shape) in want.items():
-            a = t[key]
-            if not torch.is_tensor(a) or a.device != dev or a.dtype != dtype or tuple(a.shape) != shape or not a.is_contiguous():
-                raise ValueError(f"{key} on the device must be a contiguous {dtype} {list(shape)} tensor on {dev}, got "
-                                 f"{getattr(a, 'dtype', None)} {tuple(getattr(a, 'shape', ()))} on {getattr(a, 'device', None)}")
-    else:
-        t = {key: torch.from_numpy(a).to(dev) for key, a in host.items()}
-        B = int(t["bonds"].shape[0])
-    if out is None:
-        out = torch.empty((T, 2), dtype=torch.int32, device=dev)
-    elif out.device != dev or out.dtype != torch.int32 or tuple(out.shape) != (T, 2) or not out.is_contiguous():
-        raise RuntimeError(f"out must be a contiguous int32 [{T}, 2] tensor on {dev}, got {out.dtype} {tuple(out.shape)} on {out.device}")
-    if bond_frames is False:
-        bond_frames = None
-    elif bond_frames is None:
-        bond_frames = torch.zeros((B,), dtype=torch.int32, device=dev)  # (zeros: with T == 0 the call writes nothing)
-    elif bond_frames.device != dev or bond_frames.dtype != torch.int32 or tuple(bond_frames.shape) != (B,) or not bond_frames.is_contiguous():
-        raise RuntimeError(f"bond_frames must be a contiguous int32 [{B}] tensor on {dev}, got {bond_frames.dtype} {tuple(bond_frames.shape)} on {bond_frames.device}")
+    B = int(tables["bonds"].shape[0])
+    want = {"clash_s": (torch.float32, (n * (n - 1) // 2,)), "bonds": (torch.int32, (B, 2)), "bond_lo_s": (torch.float32, (B,)),
+            "bond_hi_s": (torch.float32, (B,))}
+    t = {key: _table(key, f"{dtype} {list(shape)}", tables[key], on_device, dev, dtype, shape) for key, (dtype, shape) in want.items()}
+    out = _result("out", out, (T, 2), torch.int32, dev)
+    # (zeros: with T == 0 the call writes nothing)
+    bond_frames = None if bond_frames is False else _result("bond_frames", bond_frames, (B,), torch.int32, dev, fill=0)
     with torch.cuda.device(dev):
         if T == 0 and bond_frames is not None:
             bond_frames.zero_()

@@ -21,15 +21,14 @@ from __future__ import annotations
 
 import json
 import os
-import zipfile
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from .features import internal_coords_host, torsion_indices
-
-MAX_CUTS = 64
+from .meters import TrajectoryMeter, save_npz  # noqa: F401  (save_npz: importable from here as before)
+from .native import HIST_MAX_BINS, HIST_MAX_CUTS as MAX_CUTS, check_cuts
 
 
 def sample_counts(T: int) -> List[int]:
@@ -67,16 +66,6 @@ def phi_psi_pairs(mol: dict, pairing: str = "reference") -> Tuple[np.ndarray, np
     return index, np.array(pairs, dtype=np.int32).reshape(-1, 2), pair_labels
 
 
-def _check_cuts(cuts, T: int) -> np.ndarray:
-    c = np.asarray(cuts)
-    if c.ndim != 1 or c.dtype.kind not in "iu" or not 1 <= c.shape[0] <= MAX_CUTS:
-        raise ValueError(f"cuts must be 1 to {MAX_CUTS} integers, got {c.dtype} {tuple(c.shape)}")
-    c = c.astype(np.int64)
-    if c[0] < 1 or c[-1] > T or (np.diff(c) <= 0).any():
-        raise ValueError(f"cuts must ascend strictly within [1, {T}], got {c.tolist()}")
-    return c
-
-
 def histogram_host(angles, pairs, bins: int, cuts) -> Tuple[np.ndarray, np.ndarray]:
     """``angles [T, W]`` (radians, any float type), ``pairs [P, 2]`` (x column, y column), ``cuts`` (1 to 64 frame counts, strictly ascending
     in ``[1, T]``) -> ``(counts uint32 [C, P, bins, bins], skipped int64 [C, P])``: SEGMENT ``c`` holds the frames ``cuts[c-1] <= t <
@@ -98,7 +87,7 @@ def histogram_host(angles, pairs, bins: int, cuts) -> Tuple[np.ndarray, np.ndarr
     if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 1:
         raise ValueError(f"bins must be a positive integer, got {bins!r}")
     bins = int(bins)
-    c = _check_cuts(cuts, T)
+    c = check_cuts(cuts, T)
     edges = np.linspace(-np.pi, np.pi, bins + 1)
     counts = np.zeros((c.shape[0], p.shape[0], bins, bins), dtype=np.uint32)
     skipped = np.zeros((c.shape[0], p.shape[0]), dtype=np.int64)
@@ -157,19 +146,7 @@ def js_divergence_host(counts, ref_counts) -> Dict[str, np.ndarray]:
     return {"pooled": pooled, "per_pair": per_pair}
 
 
-def save_npz(path: str, **arrays) -> None:
-    """``np.savez`` with a fixed time stamp in the archive: the same arrays give the same bytes (``np.load`` reads it as any ``.npz``)."""
-    tmp = path + ".tmp"
-    with zipfile.ZipFile(tmp, "w", zipfile.ZIP_STORED, allowZip64=True) as z:
-        for name, a in arrays.items():
-            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.external_attr = 0o600 << 16
-            with z.open(info, "w", force_zip64=True) as f:
-                np.lib.format.write_array(f, np.ascontiguousarray(a), allow_pickle=False)
-    os.replace(tmp, path)
-
-
-class RamachandranMetrics:
+class RamachandranMetrics(TrajectoryMeter):
     """The meter of one dataset (the ``TrajectoryMetric`` protocol `callbacks.TrajectoryMetricCallback` drives): per chain and for the
     joined trajectory the (phi, psi) histograms and the curve JS divergence against the number of samples, written under
     ``<output_dir>/<label>/ramachandran/`` on rank 0:
@@ -193,92 +170,45 @@ class RamachandranMetrics:
 
     Out of scope: plots, animations, wandb and the sliced Wasserstein distance of the reference's class."""
 
+    DIRECTORY = "ramachandran"
+
     def __init__(self, dataset, sample_key: str = "xhat_traj", bins: int = 100, pairing: str = "reference", reference=None,
                  output_dir: str = "sampler", device: str = "auto", **_):
-        if device not in ("auto", "host", "device"):
-            raise ValueError(f"device must be 'auto', 'host' or 'device', got {device!r}")
+        super().__init__(dataset, sample_key, output_dir, device)
         if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 1:
             raise ValueError(f"bins must be a positive integer, got {bins!r}")
         mol = getattr(dataset, "molecule", None)
         if mol is None:
             raise ValueError(f"RamachandranMetrics: the dataset of label {dataset.label()!r} has no molecule to find phi and psi in")
-        self.dataset = dataset
-        self.label = dataset.label()
-        self.sample_key = sample_key
         self.bins = int(bins)
         self.pairing = pairing
         self.reference = reference
-        self.output_dir = output_dir
-        self.mode = device
+        self.n_atoms = len(mol["atom_names"])
         self.index, self.pairs, self.pair_labels = phi_psi_pairs(mol, pairing)
         _, self.torsion_labels = torsion_indices(mol, backbone=True, sidechain=False)
         self.torsion_labels = [l for l in self.torsion_labels if l.startswith(("PHI ", "PSI "))]
-        self.torch_device: Optional[torch.device] = None
         self.ref_counts: Optional[np.ndarray] = None  # uint32 [P, B, B]
-        self._dev: dict = {}  # device -> (index, pairs, ref counts) uploaded once
-        self.num_chains_seen = 0
-        self.joined_frames = 0
         P, B = int(self.pairs.shape[0]), self.bins
         self.joined_counts = np.zeros((P, B, B), dtype=np.uint64)
         self.joined_skipped = np.zeros((P,), dtype=np.int64)
         self._joined_prefix: Dict[int, np.ndarray] = {}  # joined cut 100 * 2^i -> counts of the first that many joined frames
-        self._pending: list = []
         self._last_joined: Optional[float] = None
 
-    # ---- protocol ------------------------------------------------------------------------------------------------------------------------
+    def _device_fits(self) -> bool:
+        return self.bins <= HIST_MAX_BINS
 
-    def to(self, device):
-        self.torch_device = torch.device(device) if device is not None else None
-        return self
-
-    def _is_rank_zero(self) -> bool:
-        from . import dist
-
-        return dist.rank_world()[0] == 0
-
-    def _dir(self) -> str:
-        d = os.path.join(self.output_dir, self.label, "ramachandran")
-        os.makedirs(d, exist_ok=True)
-        return d
+    def _device_needs(self) -> str:
+        return "RamachandranMetrics(device='device') needs float32 sample tensors on a GPU and bins <= 128"
 
     def _device_path(self, t) -> bool:
-        """Whether frames ``t`` (a tensor or an array) go through the kernels."""
-        if self.mode == "host" or self.pairs.shape[0] == 0:
-            return False
-        ok = torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and self.bins <= 128
-        if ok:
-            try:
-                from . import _lib
-
-                _lib.load()
-            except RuntimeError:
-                if self.mode == "device":
-                    raise
-                ok = False
-        if not ok and self.mode == "device":
-            raise RuntimeError("RamachandranMetrics(device='device') needs float32 sample tensors on a GPU and bins <= 128")
-        return ok
+        return self.pairs.shape[0] > 0 and super()._device_path(t)  # (no pair: nothing to count on either path)
 
     def _uploaded(self, dev):
-        if dev not in self._dev:
+        if dev not in self._dev:  # (index, pairs, ref counts)
             self._dev[dev] = [torch.from_numpy(self.index).to(dev), torch.from_numpy(self.pairs).to(dev), None]
         if self._dev[dev][2] is None and self.ref_counts is not None:  # (the reference histogram itself is made with the first two)
             self._dev[dev][2] = torch.from_numpy(self.ref_counts.view(np.int32)).to(dev)
         return self._dev[dev]
-
-    def _reference_frames(self):
-        ref = self.reference
-        if ref is None:
-            ref = getattr(self.dataset, "xyz", None)
-        if ref is None:
-            return None
-        if isinstance(ref, (str, os.PathLike)):
-            ref = np.load(ref)
-        if not torch.is_tensor(ref):
-            ref = torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32))
-        if ref.ndim != 3 or ref.shape[2] != 3 or ref.shape[1] != len(self.dataset.molecule["atom_names"]):
-            raise ValueError(f"the reference frames of {self.label!r} must have shape [T, {len(self.dataset.molecule['atom_names'])}, 3], got {tuple(ref.shape)}")
-        return ref if ref.shape[0] > 0 else None
 
     def _segments(self, frames, cuts: List[int]):
         """Raw frames ``[T, n, 3]`` -> (segment counts [C, P, B, B], skipped [C, P]) for ``cuts``: device tensors (int32) on the device
@@ -305,17 +235,11 @@ class RamachandranMetrics:
 
     def on_sample_start(self):
         P, B = int(self.pairs.shape[0]), self.bins
-        ref = self._reference_frames()
+        ref = self._reference_frames(self.n_atoms, "the reference frames of", self.reference)
         if ref is not None and P > 0:
             total = np.zeros((P, B, B), dtype=np.uint64)
-            use_gpu = (self.mode != "host" and self.torch_device is not None and self.torch_device.type == "cuda" and ref.dtype == torch.float32
-                       and self.bins <= 128)
             for t0 in range(0, int(ref.shape[0]), self.REFERENCE_CHUNK):
-                chunk = ref[t0 : t0 + self.REFERENCE_CHUNK]
-                if use_gpu and not chunk.is_cuda:
-                    chunk = chunk.to(self.torch_device)
-                elif not use_gpu and chunk.is_cuda:
-                    chunk = chunk.cpu()
+                chunk = self._on_compute_device(ref[t0 : t0 + self.REFERENCE_CHUNK])
                 counts, _ = self._segments(chunk, [int(chunk.shape[0])])
                 counts = counts.cpu().numpy().view(np.uint32) if torch.is_tensor(counts) else counts
                 total += counts[0]
@@ -334,17 +258,11 @@ class RamachandranMetrics:
             save_npz(os.path.join(d, "true_traj.npz"), counts=self.ref_counts)
 
     def update(self, sample) -> None:
-        x = sample[self.sample_key]
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"Invalid sample shape: {tuple(x.shape)}, expected (num_atoms, num_frames, 3).")
-        index = self.num_chains_seen
-        self.num_chains_seen += 1
-        T = int(x.shape[1])
+        index, frames, off = self._next_chain(sample)
+        T = int(frames.shape[0])
         if T == 0 or self.pairs.shape[0] == 0:
             return
-        frames = x.transpose(0, 1) if torch.is_tensor(x) else np.transpose(np.asarray(x), (1, 0, 2))  # [T, n, 3]: a view of the RAW chain
         own = sample_counts(T)
-        off = self.joined_frames
         inside = [100 * 2 ** i - off for i in range(10) if off < 100 * 2 ** i <= off + T]  # the joined trajectory's cuts, in local frames
         cuts = sorted(set(own) | set(inside))
         seg, skipped = self._segments(frames, cuts)
@@ -367,9 +285,7 @@ class RamachandranMetrics:
     def compute(self) -> Dict[str, float]:
         """Brings the counts and JSD values of the chains seen since the last call to the host, adds them to the joined trajectory, writes
         ``<i>.npz`` and ``joined.npz`` (rank 0) and returns the joined trajectory's last pooled JSD."""
-        pending, self._pending = self._pending, []
-        write = self._is_rank_zero()
-        d = self._dir() if write and pending else None
+        pending, write, d = self._take_pending()
         gpu = None
         for rec in pending:
             if torch.is_tensor(rec["counts"]):
@@ -402,10 +318,3 @@ class RamachandranMetrics:
         if write:
             save_npz(os.path.join(d, "joined.npz"), **out)
         return {} if self._last_joined is None else {f"{self.label}/js_divergence/pred_traj_joined": self._last_joined}
-
-    def on_after_sample_batch(self) -> None:
-        pass
-
-    def on_sample_end(self) -> None:
-        if self._pending:
-            self.compute()

@@ -59,13 +59,9 @@ def superpose(frames, ref):
     there by the HIP kernel (no copy of a strided chain view) when the native library loads; everything else goes through
     `superpose_host`.  Tensors in, tensors out (on the device of ``frames``); arrays in, arrays out."""
     if torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.float32:
-        try:
-            from . import _lib, native
+        from . import _lib, native
 
-            _lib.load()
-        except RuntimeError:
-            native = None
-        if native is not None:
+        if _lib.available():
             ref_d = torch.as_tensor(ref, dtype=torch.float32, device=frames.device) if not torch.is_tensor(ref) else ref.to(frames.device, torch.float32)
             return native.superpose_frames(frames, ref_d)
     aligned, rmsd = superpose_host(frames, ref)

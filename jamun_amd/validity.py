@@ -36,7 +36,8 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
-from .ramachandran import save_npz
+from .meters import TrajectoryMeter, save_npz
+from .native import VALIDITY_MAX_ATOMS
 
 # The reference's two tables (nm), value for value.  Its covalent radius of sulphur, 1.005, is evidently a typo for 0.105; it is kept so that
 # the default reproduces the reference's numbers (pass ``covalent_radii={"S": 0.105}`` to correct it).
@@ -231,7 +232,7 @@ def frame_factor(T: int, num_molecules_per_trajectory: Optional[int]) -> int:
     return 1 if num_molecules_per_trajectory is None else max(int(T) // int(num_molecules_per_trajectory), 1)
 
 
-class ChemicalValidityMetrics:
+class ChemicalValidityMetrics(TrajectoryMeter):
     """The meter of one dataset (the ``TrajectoryMetric`` protocol `callbacks.TrajectoryMetricCallback` drives; the reference's
     ``ChemicalValidityMetrics``): per checked frame the share of clashing non-bonded pairs and of bonds of a wrong length, written under
     ``<output_dir>/<label>/chemical_validity/`` on rank 0:
@@ -256,69 +257,30 @@ class ChemicalValidityMetrics:
     ``<label>/mean_bond_length_issues/pred_traj_<i>`` for the chains new since the last call, and the two ``.../true_traj`` keys when the
     dataset has frames of its own."""
 
+    DIRECTORY = "chemical_validity"
+
     def __init__(self, dataset, volume_exclusion_tolerance: float, bond_length_tolerance: float,
                  num_molecules_per_trajectory: Optional[int] = 100, sample_key: str = "xhat_traj", output_dir: str = "sampler",
                  device: str = "auto", vdw_radii: Optional[dict] = None, covalent_radii: Optional[dict] = None, **_):
-        if device not in ("auto", "host", "device"):
-            raise ValueError(f"device must be 'auto', 'host' or 'device', got {device!r}")
+        super().__init__(dataset, sample_key, output_dir, device)
         k = num_molecules_per_trajectory
         if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1):
             raise ValueError(f"num_molecules_per_trajectory must be a positive integer or None, got {k!r}")
         mol = getattr(dataset, "molecule", None)
         if mol is None:
             raise ValueError(f"ChemicalValidityMetrics: the dataset of label {dataset.label()!r} has no molecule")
-        self.dataset = dataset
-        self.label = dataset.label()
-        self.sample_key = sample_key
-        self.output_dir = output_dir
-        self.mode = device
         self.num_molecules_per_trajectory = None if k is None else int(k)
         self.tables = validity_tables(mol, volume_exclusion_tolerance, bond_length_tolerance, vdw_radii, covalent_radii)
         self.n_atoms = int(self.tables["n_atoms"])
-        self.torch_device: Optional[torch.device] = None
-        self._dev: dict = {}  # device -> the tables uploaded once
-        self.num_chains_seen = 0
-        self.joined_frames = 0
         self._joined: List[dict] = []  # per chain, on the host: frame_indices (offset), counts [K, 2], bond_frames [B]
-        self._pending: list = []
         self._true: Optional[Dict[str, float]] = None
 
-    # ---- protocol ------------------------------------------------------------------------------------------------------------------------
+    def _device_fits(self) -> bool:
+        return self.n_atoms <= VALIDITY_MAX_ATOMS
 
-    def to(self, device):
-        self.torch_device = torch.device(device) if device is not None else None
-        return self
-
-    def _is_rank_zero(self) -> bool:
-        from . import dist
-
-        return dist.rank_world()[0] == 0
-
-    def _dir(self) -> str:
-        d = os.path.join(self.output_dir, self.label, "chemical_validity")
-        os.makedirs(d, exist_ok=True)
-        return d
-
-    def _device_path(self, t) -> bool:
-        """Whether frames ``t`` (a tensor or an array) go through the kernel."""
-        if self.mode == "host":
-            return False
-        from . import native
-
-        ok = torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and self.n_atoms <= native.VALIDITY_MAX_ATOMS
-        if ok:
-            try:
-                from . import _lib
-
-                _lib.load()
-            except RuntimeError:
-                if self.mode == "device":
-                    raise
-                ok = False
-        if not ok and self.mode == "device":
-            raise RuntimeError(f"ChemicalValidityMetrics(device='device') needs float32 sample tensors on a GPU and a molecule of at most "
-                               f"{native.VALIDITY_MAX_ATOMS} atoms (this one has {self.n_atoms})")
-        return ok
+    def _device_needs(self) -> str:
+        return (f"ChemicalValidityMetrics(device='device') needs float32 sample tensors on a GPU and a molecule of at most "
+                f"{VALIDITY_MAX_ATOMS} atoms (this one has {self.n_atoms})")
 
     def _counts(self, frames):
         """Frames ``[K, n, 3]`` -> (counts [K, 2], bond_frames [B]): int32 device tensors on the device path, uint32 arrays on the host path."""
@@ -346,31 +308,13 @@ class ChemicalValidityMetrics:
         factor = frame_factor(int(frames.shape[0]), self.num_molecules_per_trajectory)
         return frames[::factor], np.arange(0, int(frames.shape[0]), factor, dtype=np.int64)
 
-    def _reference_frames(self):
-        ref = getattr(self.dataset, "xyz", None)
-        if ref is None:
-            return None
-        if not torch.is_tensor(ref):
-            ref = torch.from_numpy(np.ascontiguousarray(ref, dtype=np.float32))
-        if ref.ndim != 3 or ref.shape[2] != 3 or ref.shape[1] != self.n_atoms:
-            raise ValueError(f"the frames of the dataset {self.label!r} must have shape [T, {self.n_atoms}, 3], got {tuple(ref.shape)}")
-        return ref if ref.shape[0] > 0 else None
-
     def on_sample_start(self):
-        from . import native
-
         write = self._is_rank_zero()
-        ref = self._reference_frames()
+        ref = self._reference_frames(self.n_atoms, "the frames of the dataset")
         true = None
         if ref is not None:
             sub, idx = self._select(ref)
-            use_gpu = (self.mode != "host" and self.torch_device is not None and self.torch_device.type == "cuda" and ref.dtype == torch.float32
-                       and self.n_atoms <= native.VALIDITY_MAX_ATOMS)
-            if use_gpu and not sub.is_cuda:
-                sub = sub.to(self.torch_device)
-            elif not use_gpu and sub.is_cuda:
-                sub = sub.cpu()
-            true = self._arrays(idx, *self._counts(sub))
+            true = self._arrays(idx, *self._counts(self._on_compute_device(sub)))
             self._true = {f"{self.label}/mean_volume_exclusion_issues/true_traj": float(np.mean(true["volume_exclusion_issues"])),
                           f"{self.label}/mean_bond_length_issues/true_traj": float(np.mean(true["bond_length_issues"]))}
         if not write:
@@ -388,26 +332,19 @@ class ChemicalValidityMetrics:
             save_npz(os.path.join(d, "true_traj.npz"), **true)
 
     def update(self, sample) -> None:
-        x = sample[self.sample_key]
-        if x.ndim != 3 or x.shape[2] != 3:
-            raise ValueError(f"Invalid sample shape: {tuple(x.shape)}, expected (num_atoms, num_frames, 3).")
-        index = self.num_chains_seen
-        self.num_chains_seen += 1
-        T = int(x.shape[1])
+        index, frames, off = self._next_chain(sample)
+        T = int(frames.shape[0])
         if T == 0:
             return
-        frames = x.transpose(0, 1) if torch.is_tensor(x) else np.transpose(np.asarray(x), (1, 0, 2))  # [T, n, 3]: a view of the chain
         sub, idx = self._select(frames)
         counts, bond_frames = self._counts(sub)  # (on the device path: queued, nothing read back)
-        self._pending.append({"index": index, "frame_indices": idx, "counts": counts, "bond_frames": bond_frames, "joined_at": self.joined_frames})
-        self.joined_frames += T
+        self._pending.append({"index": index, "frame_indices": idx, "counts": counts, "bond_frames": bond_frames, "joined_at": off})
+        self.joined_frames = off + T
 
     def compute(self) -> Dict[str, float]:
         """Brings the counts of the chains seen since the last call to the host, writes ``<i>.npz`` and ``joined.npz`` (rank 0) and
         returns the chains' mean fractions."""
-        pending, self._pending = self._pending, []
-        write = self._is_rank_zero()
-        d = self._dir() if write and pending else None
+        pending, write, d = self._take_pending()
         out: Dict[str, float] = {}
         for rec in pending:
             a = self._arrays(rec["frame_indices"], rec["counts"], rec["bond_frames"])
@@ -424,10 +361,3 @@ class ChemicalValidityMetrics:
         if self._true is not None:
             out.update(self._true)
         return out
-
-    def on_after_sample_batch(self) -> None:
-        pass
-
-    def on_sample_end(self) -> None:
-        if self._pending:
-            self.compute()

@@ -8,8 +8,6 @@ pair of columns meets finite-finite, finite-NaN and NaN-NaN frames) followed by 
 `numpy_rule(x, y, bins)` is the pinned rule: ``np.histogram2d`` of the clipped float64 values of the frames whose x and y are finite.
 
 MOLECULES.  The Ala-Gly dipeptide of the trajectory tests, and `synth.peptide` for the tripeptide and the five-residue chain.
-
-`StubSampler` is the sampler a `TrajectoryMetricCallback` needs: ``fabric.device``, ``fabric.log_dict`` (kept in ``logged``).
 """
 import functools
 
@@ -75,35 +73,6 @@ def random_counts(C: int, P: int, B: int, seed: int, density: float = 0.3) -> np
     """uint32 [C, P, B, B] segment counts with empty bins (a share ``1 - density`` of them) and counts up to 1000."""
     rng = np.random.RandomState(seed)
     return (rng.randint(1, 1000, size=(C, P, B, B)) * (rng.uniform(size=(C, P, B, B)) < density)).astype(np.uint32)
-
-
-class _Fabric:
-    def __init__(self, device):
-        self.device = device
-        self.logged = []
-
-    def log_dict(self, d):
-        self.logged.append(dict(d))
-
-
-class StubSampler:
-    is_global_zero = True
-    world_size = 1
-    global_step = 0
-
-    def __init__(self, device):
-        self.device = device
-        self.fabric = _Fabric(device)
-
-
-def run(cb, batches, sampler):
-    cb.on_sample_start(sampler)
-    for b in batches:
-        cb.on_after_sample_batch(b, sampler)
-        if hasattr(cb, "flush"):
-            cb.flush()
-    cb.on_sample_end(sampler)
-    return cb
 
 
 def chain_frames(sample) -> np.ndarray:

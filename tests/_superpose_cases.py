@@ -280,28 +280,8 @@ def milli_angstrom(frames_nm: np.ndarray) -> np.ndarray:
     return np.rint((np.asarray(frames_nm, dtype=np.float32) * np.float32(10.0)).astype(np.float64) * 1000.0).astype(np.int64)
 
 
-class CaseDataset:
-    def __init__(self, mol, label):
-        self.molecule, self._label = mol, label
-
-    def label(self):
-        return self._label
-
-
 class CaseSampler:
     is_global_zero = True; world_size = 1; global_step = 0
 
     def __init__(self, device):
         self.device = device
-
-
-def tree(root: str) -> dict:
-    """relative path -> bytes of every file under ``root``."""
-    import os
-
-    out = {}
-    for dp, _, fs in os.walk(root):
-        for f in fs:
-            p = os.path.join(dp, f)
-            out[os.path.relpath(p, root)] = open(p, "rb").read()
-    return out

@@ -64,6 +64,53 @@ def test_error_reporting_without_gpu():
         _lib.check(code)
 
 
+def _frames_entry_call(lib, entry: str, args: list):
+    """One call of a frames entry with the arguments of tests/golden/frames_api_refusals.json -> (code, error text, value written or None).
+    An integer argument stands for itself.  For a pointer, None is null, "host" the address of 64 bytes of host memory (a non-null
+    pointer for the entries that test null first; every case that passes one ends before any launch), "host+1" that address plus one,
+    "out" an int64 to receive a value, and a list an int32 host array.  The error slot is first set to a known text by a refused
+    jamun_model_create, so that a call that succeeds shows the slot untouched."""
+    import ctypes as C
+
+    from jamun_amd import _lib
+
+    host = C.create_string_buffer(64)
+    value = C.c_int64(-1)
+    keep, call = [], []
+    for a, ctype in zip(args, _lib.SYMBOLS[entry][1], strict=True):
+        if isinstance(a, int):
+            call.append(a)
+        elif a is None:
+            call.append(None)
+        elif a in ("host", "host+1"):
+            call.append(C.addressof(host) + (a == "host+1"))
+        elif a == "out":
+            call.append(C.byref(value))
+        else:
+            keep.append((C.c_int32 * len(a))(*a))
+            call.append(C.cast(keep[-1], C.c_void_p))
+    assert lib.jamun_model_create(None, None, 0, C.byref(C.c_void_p())) != 0
+    code = getattr(lib, entry)(*call)
+    return code, lib.jamun_last_error().decode(), (value.value if "out" in args else None)
+
+
+def test_frames_entries_refuse_as_the_parent_did():
+    """The eight entries of csrc/jamun_frames.cpp answer every case of tests/golden/frames_api_refusals.json (recorded from the library
+    before they moved out of jamun_api.cpp and came to share their checks) with the same code and the same text.  No case needs a GPU
+    or would reach a launch if its refusal were lost: the device pointers are null, the call has nothing to write, or a later refusal ends it."""
+    import json
+
+    from jamun_amd import _lib
+
+    lib = _lib.load()
+    cases = json.load(open(os.path.join(ROOT, "tests", "golden", "frames_api_refusals.json")))
+    assert {c["entry"] for c in cases} == {"jamun_pdb_models_nbytes", "jamun_encode_pdb_models", "jamun_encode_dcd_frames", "jamun_superpose_frames",
+                                           "jamun_internal_coords", "jamun_hist2d_pairs", "jamun_js_divergence", "jamun_validity_counts"}
+    for c in cases:
+        code, error, value = _frames_entry_call(lib, c["entry"], c["args"])
+        assert (code, error, value) == (c["code"], c["error"], c["value"]), c
+
+
 def test_product_does_not_import_oracle():
     pkg = os.path.join(ROOT, "jamun_amd")
     for dp, _, files in os.walk(pkg):

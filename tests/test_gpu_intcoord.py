@@ -9,45 +9,19 @@ import pytest
 import torch
 
 import _intcoord_cases as ic
-from _superpose_cases import CaseDataset, tree
+from _frames_common import CaseDataset, _dev, chain_view as _chain_view, guarded, intact, tree
 from _traj_molecules import dipeptide
 
 pytestmark = pytest.mark.gpu
 
 TOL_A, TOL_D = ic.TORSION_TOL_RAD, ic.DIST_TOL_NM
-SENTINEL = 12345.0
-PAD = 64  # sentinel floats in front of and behind an output
-
-
-def _dev():
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def _chain_view(frames: np.ndarray, dev) -> torch.Tensor:
-    """``frames`` [T, n, 3] as the callback sees a chain: ``block[1].transpose(0, 1)`` of a 3-chain [chains, n, T, 3] block (no copy)."""
-    T, n, _ = frames.shape
-    block = torch.full((3, n, T, 3), float("nan"), dtype=torch.float32, device=dev)
-    block[1] = torch.from_numpy(np.array(np.transpose(frames, (1, 0, 2)), order="C")).to(dev)
-    view = block[1].transpose(0, 1)
-    assert view.shape == (T, n, 3) and view.data_ptr() == block[1].data_ptr()
-    return view
+SENTINEL = 12345.0  # 64 of them in front of and behind an output (`guarded`)
 
 
 def _flat(frames: np.ndarray, dev) -> torch.Tensor:
     t = torch.from_numpy(np.array(frames, dtype=np.float32, order="C")).to(dev)
     assert t.is_contiguous()
     return t
-
-
-def _guarded_out(T: int, W: int, dev):
-    big = torch.full((T * W + 2 * PAD,), SENTINEL, dtype=torch.float32, device=dev)
-    return big, big[PAD : PAD + T * W].view(T, W)
-
-
-def _pads_intact(big: torch.Tensor) -> bool:
-    host = big.cpu().numpy()
-    return bool((host[:PAD] == SENTINEL).all() and (host[-PAD:] == SENTINEL).all())
 
 
 def _check(got, want, index, cossin, what):
@@ -123,11 +97,11 @@ def test_frame_and_feature_counts_around_a_wave_and_a_tile(T):
         assert sorted(set(ic.kinds(index).tolist())) == [2, 3, 4][: min(F, 3)]
         for cossin in (False, True):
             W = 2 * F if cossin else F
-            big, out = _guarded_out(T, W, dev)
+            big, out = guarded((T, W), dev, torch.float32, SENTINEL)
             got = native.internal_coords(chain, index, cossin=cossin, out=out)
             other = native.internal_coords(flat, index, cossin=cossin)
             torch.cuda.synchronize()
-            assert got.data_ptr() == out.data_ptr() and torch.equal(got, other) and _pads_intact(big)
+            assert got.data_ptr() == out.data_ptr() and torch.equal(got, other) and intact(big, SENTINEL)
             _check(got.cpu().numpy(), internal_coords_host(frames, index, cossin=cossin), index, cossin, f"T={T}, F={F}, cossin={int(cossin)}")
 
 
@@ -184,10 +158,10 @@ def test_a_row_with_an_index_out_of_range_is_nan_and_leaves_the_others_alone(cos
     m = 2 if cossin else 1
     outs = []
     for t in (good, table):
-        big, out = _guarded_out(70, 7 * m, dev)
+        big, out = guarded((70, 7 * m), dev, torch.float32, SENTINEL)
         assert _raw_call(chain, torch.from_numpy(t).to(dev), cossin, out) == 0
         torch.cuda.synchronize()
-        assert _pads_intact(big)
+        assert intact(big, SENTINEL)
         outs.append(out.cpu().numpy())
     clean, got = outs
     bad = np.zeros(got.shape, dtype=bool)
@@ -217,7 +191,7 @@ def test_out_capacity_too_small_is_invalid_and_writes_nothing():
     frames, pos = ic.rigid_case()
     chain = _chain_view(frames[:70], dev)
     index = torch.from_numpy(ic.mixed_table(pos, 7, seed=7)).to(dev)
-    big, out = _guarded_out(70, 14, dev)
+    big, out = guarded((70, 14), dev, torch.float32, SENTINEL)
     assert _raw_call(chain, index, 1, out, capacity=70 * 14 - 1) == -1  # JAMUN_ERR_INVALID
     assert _raw_call(chain, index, 0, out, capacity=70 * 7 - 1) == -1
     assert b"out_capacity" in _lib.load().jamun_last_error()

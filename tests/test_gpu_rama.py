@@ -11,7 +11,7 @@ import torch
 
 import _rama_cases as rc
 from _intcoord_cases import TORSION_TOL_RAD, _well_conditioned, tumbling_batches
-from _superpose_cases import CaseDataset, tree
+from _frames_common import CaseDataset, StubSampler, _dev, guarded, intact, run, tree
 from _traj_molecules import dipeptide
 from jamun_amd import ramachandran as R
 
@@ -22,13 +22,7 @@ pytestmark = pytest.mark.gpu
 # one sample of 1e5 does.
 JSD_TOL = 1e-12
 SENTINEL = -77
-PAD = 64
 SLICE = 4096  # JAMUN_HIST_SLICE (test_rama_host.py checks that native.HIST_SLICE mirrors the header)
-
-
-def _dev():
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return torch.device("cuda", 0)
 
 
 def _padded(a: np.ndarray, dev, pad: int = 3) -> torch.Tensor:
@@ -39,16 +33,6 @@ def _padded(a: np.ndarray, dev, pad: int = 3) -> torch.Tensor:
     view = big[:, :W]
     assert T == 1 or view.stride(0) == W + pad
     return view
-
-
-def _guarded(shape, dev):
-    n = int(np.prod(shape))
-    big = torch.full((n + 2 * PAD,), SENTINEL, dtype=torch.int32, device=dev)
-    return big, big[PAD : PAD + n].view(*shape)
-
-
-def _intact(big) -> bool:
-    return bool((big[:PAD] == SENTINEL).all().item() and (big[-PAD:] == SENTINEL).all().item())
 
 
 def _pairs(W: int, P: int) -> np.ndarray:
@@ -73,12 +57,12 @@ def test_counts_equal_the_host_specification_integer_for_integer(bins):
             pairs = _pairs(W, P)
             for cuts in rc.cut_sets(T):
                 want, want_skipped = R.histogram_host(a, pairs, bins, cuts)
-                big, out = _guarded((len(cuts), P, bins, bins), dev)
-                big_s, sk = _guarded((len(cuts), P), dev)
+                big, out = guarded((len(cuts), P, bins, bins), dev, torch.int32, SENTINEL)
+                big_s, sk = guarded((len(cuts), P), dev, torch.int32, SENTINEL)
                 got, got_skipped = native.hist2d_pairs(x, pairs, bins, cuts, out=out, skipped=sk)
                 torch.cuda.synchronize()
                 what = (T, W, P, cuts[:4])
-                assert got.data_ptr() == out.data_ptr() and _intact(big) and _intact(big_s), what
+                assert got.data_ptr() == out.data_ptr() and intact(big, SENTINEL) and intact(big_s, SENTINEL), what
                 assert np.array_equal(got.cpu().numpy().view(np.uint32), want), what
                 assert np.array_equal(got_skipped.cpu().numpy().astype(np.int64), want_skipped), what
     assert want_skipped.sum() > 0 and want.sum() > 0
@@ -121,8 +105,8 @@ def test_the_c_entries_refuse_bad_arguments_and_write_nothing():
     a = torch.zeros(T, W, device=dev)
     pairs = torch.tensor([[0, 1]], dtype=torch.int32, device=dev)
     edges = torch.from_numpy(np.linspace(-np.pi, np.pi, bins + 1)).to(dev)
-    big, out = _guarded((2, 1, bins, bins), dev)
-    big_s, sk = _guarded((2, 1), dev)
+    big, out = guarded((2, 1, bins, bins), dev, torch.int32, SENTINEL)
+    big_s, sk = guarded((2, 1), dev, torch.int32, SENTINEL)
     st = torch.cuda.current_stream().cuda_stream
 
     def call(cuts, capacity=None, b=bins, stride=W):
@@ -140,7 +124,7 @@ def test_the_c_entries_refuse_bad_arguments_and_write_nothing():
     assert (big == SENTINEL).all() and (big_s == SENTINEL).all()
     assert call([50, 100]) == 0
     torch.cuda.synchronize()
-    assert _intact(big) and out.sum().item() == 100
+    assert intact(big, SENTINEL) and out.sum().item() == 100
     pooled = torch.zeros(2, dtype=torch.float64, device=dev)
     per_pair = torch.zeros(2, 1, dtype=torch.float64, device=dev)
     js = lambda n_ref, b=bins: lib.jamun_js_divergence(out.data_ptr(), 2, 1, b, out.data_ptr(), n_ref, pooled.data_ptr(), per_pair.data_ptr(), st)
@@ -252,8 +236,8 @@ def test_meter_on_device_tensors_writes_the_host_paths_files_except_at_bin_edges
     runs = {}
     for mode in ("device", "host"):
         cb = RamachandranMetricsCallback([ds], output_dir=str(tmp_path / mode), bins=bins, reference=reference, device=mode)
-        smp = rc.StubSampler(dev)
-        rc.run(cb, batches, smp)
+        smp = StubSampler(dev)
+        run(cb, batches, smp)
         runs[mode] = (cb, smp, tmp_path / mode / "m" / "ramachandran")
     d, h = runs["device"][2], runs["host"][2]
     assert sorted(os.listdir(d)) == sorted(os.listdir(h)) == sorted([f"{i}.npz" for i in range(2 * chains)] + ["joined.npz", "pairs.json", "true_traj.npz"])
@@ -300,7 +284,7 @@ def test_metric_files_are_the_same_bytes_with_superposed_trajectory_files(tmp_pa
         root = tmp_path / ("on" if superpose else "off")
         save = SaveTrajectoryCallback([ds], output_dir=str(root), encode="device", superpose=superpose)
         meter = RamachandranMetricsCallback([ds], output_dir=str(root), bins=50, reference=reference)
-        smp = rc.StubSampler(dev)
+        smp = StubSampler(dev)
         for cb in (save, meter):
             cb.on_sample_start(smp)
         for b in batches:

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _superpose_cases as sc
+from _frames_common import CaseDataset, _dev, chain_view as _chain_view, tree
 from _traj_molecules import dipeptide
 
 pytestmark = pytest.mark.gpu
@@ -16,23 +17,8 @@ RMSD_TOL_NM = sc.RMSD_TOL_NM
 SENTINEL = 12345.0
 
 
-def _dev():
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return torch.device("cuda", 0)
-
-
 def _cycled(a: np.ndarray, T: int) -> np.ndarray:
     return a[np.arange(T) % a.shape[0]]
-
-
-def _chain_view(frames: np.ndarray, dev, fill=float("nan")) -> torch.Tensor:
-    """``frames`` [T, n, 3] as the callback sees a chain: ``block[1].transpose(0, 1)`` of a 3-chain [chains, n, T, 3] block (no copy)."""
-    T, n, _ = frames.shape
-    block = torch.full((3, n, T, 3), fill, dtype=torch.float32, device=dev)
-    block[1] = torch.from_numpy(np.array(np.transpose(frames, (1, 0, 2)), order="C")).to(dev)  # (a writable copy)
-    view = block[1].transpose(0, 1)
-    assert view.shape == (T, n, 3) and view.data_ptr() == block[1].data_ptr()
-    return view
 
 
 def _check(got, got_rmsd, aligned, rmsd, what):
@@ -212,11 +198,11 @@ def test_callback_device_path_writes_the_host_path_files(tmp_path, monkeypatch, 
     mol = dipeptide()
     n, T, chains = 10, 70, 3
     batches = _tumbling_batches(mol, dev, chains, T, 2, seed=5)
-    ds = sc.CaseDataset(mol, "m")
+    ds = CaseDataset(mol, "m")
     cbs = {m: _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / m), encode=m, superpose=True), batches, dev) for m in ("device", "host")}
     raw = _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "raw"), encode="device"), batches, dev)
     assert cbs["device"]._encoder is not None and cbs["host"]._encoder is None
-    trees = {m: sc.tree(str(tmp_path / m)) for m in ("device", "host", "raw")}
+    trees = {m: tree(str(tmp_path / m)) for m in ("device", "host", "raw")}
     assert sorted(trees["device"]) == sorted(trees["host"])
     assert sorted(f for f in trees["device"] if "rmsd" not in f) == sorted(trees["raw"])
     for f, data in trees["device"].items():
@@ -249,7 +235,7 @@ def test_staging_memory_does_not_depend_on_the_frame_count(tmp_path):
     mol = dipeptide()
     sizes = []
     for T in (70, 700):
-        cb = _run(SaveTrajectoryCallback([sc.CaseDataset(mol, "m")], output_dir=str(tmp_path / str(T)), encode="device", superpose=True),
+        cb = _run(SaveTrajectoryCallback([CaseDataset(mol, "m")], output_dir=str(tmp_path / str(T)), encode="device", superpose=True),
                   _tumbling_batches(mol, dev, 3, T, 1, seed=T), dev)
         sizes.append(cb._encoder.staging_bytes())
         assert cb._encoder._aligned.numel() * 4 == traj_encode.STAGING_BYTES and not cb._dev_blocks

@@ -9,16 +9,12 @@ import numpy as np
 import pytest
 import torch
 
+from _frames_common import _dev
 from _traj_molecules import molecule, named_chain
 
 pytestmark = pytest.mark.gpu
 
 DCD_PREAMBLE = 276  # bytes of a save_dcd file in front of the coordinate records: header, title block, atom count
-
-
-def _dev():
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return torch.device("cuda", 0)
 
 
 def _expected_models(tmp_path, mol, frames: torch.Tensor, first_model: int) -> bytes:

@@ -8,32 +8,15 @@ import pytest
 import torch
 
 import _validity_cases as vc
-from _superpose_cases import CaseDataset, tree
-from _rama_cases import StubSampler, run
+from _frames_common import _dev, guarded, intact, meter_run, tree
 from _traj_molecules import dipeptide
 from jamun_amd import validity as V
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -77
-PAD = 64
 CHUNK, SPLIT, MAX_ATOMS = 64, 32, 256  # the seams of the kernel as built (test_validity_host.py checks that native mirrors the header)
 T_MAX = 129
-
-
-def _dev():
-    assert torch.cuda.is_available(), "these tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def _guarded(shape, dev):
-    n = int(np.prod(shape))
-    big = torch.full((n + 2 * PAD,), SENTINEL, dtype=torch.int32, device=dev)
-    return big, big[PAD : PAD + n].view(*shape)
-
-
-def _intact(big) -> bool:
-    return bool((big[:PAD] == SENTINEL).all().item() and (big[-PAD:] == SENTINEL).all().item())
 
 
 def _layouts(frames3: np.ndarray, T: int, dev):
@@ -71,12 +54,12 @@ def test_counts_and_bond_frames_equal_the_host_specification_integer_for_integer
         for T in (1, 63, 64, 65, T_MAX):
             for name, view, host in _layouts(frames3, T, dev):
                 want, want_bf = V.validity_counts_host(host, tables)
-                big, out = _guarded((T, 2), dev)
-                big_b, bf = _guarded((B,), dev)
+                big, out = guarded((T, 2), dev, torch.int32, SENTINEL)
+                big_b, bf = guarded((B,), dev, torch.int32, SENTINEL)
                 got, got_bf = native.validity_counts(view, on_dev, out=out, bond_frames=bf)
                 torch.cuda.synchronize()
                 what = (n, kind, T, name)
-                assert got.data_ptr() == out.data_ptr() and got_bf.data_ptr() == bf.data_ptr() and _intact(big) and _intact(big_b), what
+                assert got.data_ptr() == out.data_ptr() and got_bf.data_ptr() == bf.data_ptr() and intact(big, SENTINEL) and intact(big_b, SENTINEL), what
                 assert np.array_equal(_u32(got), want), what
                 assert np.array_equal(_u32(got_bf), want_bf), what
                 seen += want.sum(axis=0).astype(np.int64)
@@ -151,8 +134,8 @@ def test_the_c_entry_refuses_bad_arguments_and_writes_nothing():
     t = native.upload_validity_tables(tables, n, dev)
     B = tables["num_bonds"]
     x = torch.from_numpy(np.array(vc.helix_frames(n, T))).to(dev)
-    big, out = _guarded((T, 2), dev)
-    big_b, bf = _guarded((B,), dev)
+    big, out = guarded((T, 2), dev, torch.int32, SENTINEL)
+    big_b, bf = guarded((B,), dev, torch.int32, SENTINEL)
     st = torch.cuda.current_stream().cuda_stream
     p = lambda a: None if a is None else a.data_ptr()
 
@@ -175,16 +158,16 @@ def test_the_c_entry_refuses_bad_arguments_and_writes_nothing():
     want, want_bf = V.validity_counts_host(x.cpu().numpy(), tables)
     assert call(frames_of_bond=None) == 0  # (no per-bond counts asked for)
     torch.cuda.synchronize()
-    assert np.array_equal(_u32(out), want) and (big_b == SENTINEL).all() and _intact(big)
+    assert np.array_equal(_u32(out), want) and (big_b == SENTINEL).all() and intact(big, SENTINEL)
     assert call(n_bonds=0, bonds=None, lo=None, hi=None, frames_of_bond=None) == 0  # (no bonds: NULL bond pointers)
     torch.cuda.synchronize()
     assert np.array_equal(_u32(out)[:, 0], want[:, 0]) and not _u32(out)[:, 1].any()
     assert call(n_atoms=1, clash=None, n_bonds=0, bonds=None, lo=None, hi=None) == 0  # (one atom: zeros)
     torch.cuda.synchronize()
-    assert not _u32(out).any() and _intact(big)
+    assert not _u32(out).any() and intact(big, SENTINEL)
     assert call() == 0
     torch.cuda.synchronize()
-    assert np.array_equal(_u32(out), want) and np.array_equal(_u32(bf), want_bf) and _intact(big) and _intact(big_b)
+    assert np.array_equal(_u32(out), want) and np.array_equal(_u32(bf), want_bf) and intact(big, SENTINEL) and intact(big_b, SENTINEL)
     # the wrapper checks a host bond table before anything is uploaded
     for bad in ([[0, n]], [[-1, 0]], [[2, 2]]):
         with pytest.raises(ValueError, match="bond 0"):
@@ -218,14 +201,8 @@ def test_a_second_call_gives_the_same_bits_whatever_the_buffers_held(n):
 def _meter_run(root, mol, batches, dev, xyz=None, **kw):
     from jamun_amd.callbacks import ChemicalValidityMetricsCallback
 
-    ds = CaseDataset(mol, "m")
-    if xyz is not None:
-        ds.xyz = xyz
     vtol, btol = kw.pop("tolerances")
-    cb = ChemicalValidityMetricsCallback([ds], output_dir=str(root), volume_exclusion_tolerance=vtol, bond_length_tolerance=btol, **kw)
-    smp = StubSampler(dev)
-    run(cb, batches, smp)
-    return cb, smp
+    return meter_run(ChemicalValidityMetricsCallback, root, mol, batches, dev, xyz=xyz, volume_exclusion_tolerance=vtol, bond_length_tolerance=btol, **kw)
 
 
 @pytest.mark.parametrize("num", [100, None])

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import _intcoord_cases as ic
-from _superpose_cases import CaseDataset, tree
+from _frames_common import CaseDataset, tree
 from _traj_molecules import dipeptide
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

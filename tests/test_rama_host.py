@@ -9,7 +9,7 @@ import torch
 
 import _rama_cases as rc
 from _intcoord_cases import tumbling_batches
-from _superpose_cases import CaseDataset, tree
+from _frames_common import CaseDataset, StubSampler, meter_run, run, tree
 from jamun_amd import ramachandran as R
 
 
@@ -203,10 +203,7 @@ def test_native_constants_mirror_the_header():
 def _meter_run(tmp_path, name, batches, **kw):
     from jamun_amd.callbacks import RamachandranMetricsCallback
 
-    mol = rc.molecules()["AG"]
-    cb = RamachandranMetricsCallback([CaseDataset(mol, "m")], output_dir=str(tmp_path / name), **kw)
-    smp = rc.StubSampler(torch.device("cpu"))
-    rc.run(cb, batches, smp)
+    cb, smp = meter_run(RamachandranMetricsCallback, tmp_path / name, rc.molecules()["AG"], batches, torch.device("cpu"), **kw)
     return cb, smp, tmp_path / name / "m" / "ramachandran"
 
 
@@ -269,9 +266,9 @@ def test_meter_takes_the_datasets_own_frames_as_reference(tmp_path):
     ds.xyz = batches[0][0]["xhat_traj"].permute(1, 0, 2).contiguous()  # [T, n, 3], as MDtrajDataset keeps its frames
     path = tmp_path / "ref.npy"
     np.save(path, ds.xyz.numpy())
-    a = rc.run(RamachandranMetricsCallback([ds], output_dir=str(tmp_path / "xyz"), bins=10), batches, rc.StubSampler(torch.device("cpu")))
-    b = rc.run(RamachandranMetricsCallback([CaseDataset(mol, "m")], output_dir=str(tmp_path / "npy"), bins=10, reference=str(path)), batches,
-               rc.StubSampler(torch.device("cpu")))
+    a = run(RamachandranMetricsCallback([ds], output_dir=str(tmp_path / "xyz"), bins=10), batches, StubSampler(torch.device("cpu")))
+    b = run(RamachandranMetricsCallback([CaseDataset(mol, "m")], output_dir=str(tmp_path / "npy"), bins=10, reference=str(path)), batches,
+               StubSampler(torch.device("cpu")))
     assert tree(str(tmp_path / "xyz")) == tree(str(tmp_path / "npy"))
     z = np.load(tmp_path / "xyz" / "m" / "ramachandran" / "0.npz")
     assert z["js_divergence"].tolist() == [0.0] and z["num_samples"].tolist() == [60]  # chain 0 IS the reference

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import _superpose_cases as sc
+from _frames_common import CaseDataset, tree
 from _traj_molecules import dipeptide
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -150,10 +151,10 @@ def test_callback_superposes_pdb_and_dcd_keeps_npy_raw_and_writes_rmsd(tmp_path)
     mol = dipeptide()
     n, T = 10, 5
     batches = _batches(mol, chains=2, T=T, n_batches=2)
-    ds = sc.CaseDataset(mol, "m")
+    ds = CaseDataset(mol, "m")
     _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "off")), batches)
     _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "on"), superpose=True), batches)
-    off, on = sc.tree(str(tmp_path / "off")), sc.tree(str(tmp_path / "on"))
+    off, on = tree(str(tmp_path / "off")), tree(str(tmp_path / "on"))
     rmsd_files = sorted(f for f in on if f.startswith(os.path.join("m", "predicted_samples", "rmsd")))
     assert rmsd_files == [os.path.join("m", "predicted_samples", "rmsd", f"{i}.npy") for i in (0, 1, 2, 3, "joined")]
     assert sorted(set(on) - set(rmsd_files)) == sorted(off)
@@ -183,8 +184,8 @@ def test_callback_superpose_needs_a_molecule_per_label():
             return "bare"
 
     with pytest.raises(ValueError, match="bare"):
-        SaveTrajectoryCallback([sc.CaseDataset(dipeptide(), "m"), Bare()], superpose=True)
-    SaveTrajectoryCallback([sc.CaseDataset(dipeptide(), "m"), Bare()])  # off: as before
+        SaveTrajectoryCallback([CaseDataset(dipeptide(), "m"), Bare()], superpose=True)
+    SaveTrajectoryCallback([CaseDataset(dipeptide(), "m"), Bare()])  # off: as before
 
 
 def test_callback_with_the_option_off_writes_what_it_wrote_without_the_argument(tmp_path):
@@ -192,10 +193,10 @@ def test_callback_with_the_option_off_writes_what_it_wrote_without_the_argument(
 
     mol = dipeptide()
     batches = _batches(mol, chains=2, T=4, n_batches=2, seed=1)
-    ds = sc.CaseDataset(mol, "m")
+    ds = CaseDataset(mol, "m")
     _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "plain")), batches)
     _run(SaveTrajectoryCallback([ds], output_dir=str(tmp_path / "off"), superpose=False), batches)
-    plain, off = sc.tree(str(tmp_path / "plain")), sc.tree(str(tmp_path / "off"))
+    plain, off = tree(str(tmp_path / "plain")), tree(str(tmp_path / "off"))
     assert sorted(plain) == sorted(off) and plain == off
     assert not any("rmsd" in f for f in off) and len(off) == 1 + 3 * 5
 
@@ -209,7 +210,7 @@ def test_option_is_reachable_from_the_command_line(tmp_path):
     assert on["callbacks"]["save_trajectory"]["superpose"] is True
     assert "superpose" not in Cfg.resolve(cmdline.compose(args, cwd=str(tmp_path)))["callbacks"]["save_trajectory"]  # the shipped yaml is as it was
     node = {k: v for k, v in on["callbacks"]["save_trajectory"].items() if k != "datasets"}  # (the datasets would be read from init_pdbs)
-    cb = Cfg.instantiate(node, datasets=[sc.CaseDataset(dipeptide(), "m")])
+    cb = Cfg.instantiate(node, datasets=[CaseDataset(dipeptide(), "m")])
     assert cb.superpose is True
 
 

@@ -12,8 +12,7 @@ import pytest
 import torch
 
 import _validity_cases as vc
-from _rama_cases import StubSampler, run
-from _superpose_cases import CaseDataset, tree
+from _frames_common import CaseDataset, meter_run, tree
 from _traj_molecules import dipeptide, named_chain
 from jamun_amd import validity as V
 
@@ -205,13 +204,9 @@ def test_a_denominator_of_zero_gives_nan_fractions():
 def _meter_run(root, batches, mol=None, xyz=None, **kw):
     from jamun_amd.callbacks import ChemicalValidityMetricsCallback
 
-    ds = CaseDataset(mol or dipeptide(), "m")
-    if xyz is not None:
-        ds.xyz = xyz
     vtol, btol = vc.DIPEPTIDE_TOLERANCES
-    cb = ChemicalValidityMetricsCallback([ds], output_dir=str(root), volume_exclusion_tolerance=vtol, bond_length_tolerance=btol, **kw)
-    smp = StubSampler(torch.device("cpu"))
-    run(cb, batches, smp)
+    cb, smp = meter_run(ChemicalValidityMetricsCallback, root, mol or dipeptide(), batches, torch.device("cpu"), xyz=xyz,
+                        volume_exclusion_tolerance=vtol, bond_length_tolerance=btol, **kw)
     return cb, smp, root / "m" / "chemical_validity"
 
 
