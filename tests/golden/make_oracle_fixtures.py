@@ -155,7 +155,101 @@ def sampler_case(continue_chain, steps=8, num_batches=2, max_batches=None):
     return {f"xhat_traj_{b}": o["xhat_traj"] for b, o in enumerate(outs)} | {f"y_{b}": o["y"] for b, o in enumerate(outs)}
 
 
+# ---- the command-line runs of tests/test_gpu_cli.py, end to end -------------------------------------------------------
+# The oracle is fed from the source of truth, not from the product's readers (a reader bug must not cancel out): topology tensors from
+# jamun_amd.synth, positions from the file on disk through the few lines below, parameters restated from the experiment yaml.
+CLI_PARAMS = dict(delta=0.05, friction=0.7, M=1.3, inverse_temperature=0.9, score_fn_clip=40.0, save_trajectory=True)
+CLI_PARAMS_SEED = 7
+# score_fn_clip = 40 binds on some atoms and not on others: measured in the oracle run (2 x 12 steps, 40 atoms; stored as `clip_share`,
+# asserted in tests/test_cli_cases_host.py) 0.384 of the per-atom score norms are above it.  The norms have two sources: the noise,
+# about chi_3 / sigma = 25 chi_3 (median 38), and on the first steps the centroid of the file's coordinates, which x-hat removes and y
+# keeps (0.35 nm / sigma^2 = 220).  A clip of 0.5 or 3 binds on every atom (share 1: indistinguishable from a fixed step length).
+# the dipeptides of test_jamun_sample_uncapped_2aa_directory_end_to_end in the order the test lists them (the seed of a code is its place here)
+CLI_2AA_CODES = ["AG", "GG", "WW", "FY", "KR", "PH", "CM", "DE", "NQ", "ST", "IL", "VA", "RK", "HP", "MC", "ED", "QN", "TS", "LI", "YF",
+                 "GW", "WA", "AV", "SG", "PP", "KE", "DR", "HH"]
+
+
+def pdb_heavy_positions_nm(path):
+    """Decimal columns 31-54 of the ATOM records of the first model, Angstrom / 10 as float32, and which records are not hydrogens
+    (element columns 77-78)."""
+    xyz, heavy = [], []
+    for line in open(path):
+        if line.startswith("ENDMDL"):
+            break
+        if line.startswith("ATOM  "):
+            xyz.append([float(line[30:38]), float(line[38:46]), float(line[46:54])])
+            heavy.append(line[76:78].strip() != "H")
+    return torch.from_numpy(np.asarray(xyz, dtype=np.float32) / np.float32(10.0)), np.asarray(heavy)
+
+
+def _topology(mol):
+    return {k: v for k, v in mol.items() if torch.is_tensor(v) and k != "pos"}
+
+
+def cli_oracle_run(mols, seed, steps, num_batches, mcmc, max_steps=None, max_batches=None):
+    """`sampler_loop` over the collated molecules with the stable checkpoint, TorchNoise(seed) and continue_chain, as `jamun_sample` runs
+    it; returns the inputs the oracle consumed, per batch xhat_traj / y, and the share of per-atom score norms above the clip."""
+    topo = og.collate(mols)
+    p = {k: v.to(torch.float32) for k, v in synth.synthetic_state_dict(output_gain=GAINS["stable"]).items()}
+    hp = od.default_hparams()
+    steps = steps if max_steps is None else min(steps, max_steps)
+    nb = num_batches if max_batches is None else min(num_batches, max_batches)
+    norms = []
+
+    def score_fn(y):
+        s = od.score(y, topo, SIGMA, p, hp)
+        norms.append(torch.linalg.vector_norm(s, dim=-1))
+        return s
+
+    outs = ow.sampler_loop(topo["pos"], score_fn, lambda y: od.xhat(y, topo, SIGMA, p, hp), ow.baoab, SIGMA, nb, True, ow.TorchNoise(seed),
+                           steps=steps, **mcmc)
+    res = {k: topo[k] for k in ("pos", "atom_type_index", "atom_code_index", "residue_code_index", "residue_sequence_index", "bonds", "ptr")}
+    res["clip_share"] = (torch.cat(norms) > mcmc["score_fn_clip"]).float().mean()
+    for b, o in enumerate(outs):
+        res[f"xhat_traj_{b}"], res[f"y_{b}"] = o["xhat_traj"], o["y"]
+    return res
+
+
+def cli_cfg1_case(mcmc, seed, steps, max_steps=None, max_batches=None):
+    """`jamun_sample experiment=sample_custom ++init_pdbs=[uncapped_AG.pdb] repeat_init_samples=4 num_batches=2` on the AG dipeptide
+    file as tests/test_gpu_cli.py writes it."""
+    import tempfile
+
+    from jamun_amd import pdb
+
+    mol = dict(synth.ag_dipeptide(), elements=["N", "C", "C", "C", "O", "N", "C", "C", "O", "O"], residue_ids=[1] * 5 + [2] * 5)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "uncapped_AG.pdb")
+        pdb.write_pdb(path, mol, mol["pos"][None])
+        pos, heavy = pdb_heavy_positions_nm(path)
+    assert heavy.all() and pos.shape == mol["pos"].shape
+    return cli_oracle_run([dict(_topology(synth.ag_dipeptide()), pos=pos)] * 4, seed, steps, 2, mcmc, max_steps, max_batches)
+
+
+def cli_2aa_case(steps=12, max_steps=None, max_batches=None):
+    """`jamun_sample experiment=sample_timewarp_2AA ++init_datasets.num_frames=1` over the 28-code tree of tests/test_gpu_cli.py: one walker
+    per code in sorted order (the reference sorts the codes of a directory, data/_utils.py:94), each at frame 0 of its `positions`."""
+    import tempfile
+
+    mols = []
+    order = sorted(CLI_2AA_CODES)
+    with tempfile.TemporaryDirectory() as d:
+        synth.write_timewarp_tree(d, CLI_2AA_CODES, n_frames=2)
+        for code in order:
+            top = _topology(synth.peptide(code, seed=CLI_2AA_CODES.index(code)))
+            _, heavy = pdb_heavy_positions_nm(os.path.join(d, f"{code}-traj-state0.pdb"))
+            frame0 = np.load(os.path.join(d, f"{code}-traj-arrays.npz"))["positions"][0]
+            assert frame0.dtype == np.float32 and frame0.shape[0] == heavy.shape[0] and int(heavy.sum()) == top["atom_type_index"].shape[0]
+            mols.append(dict(top, pos=torch.from_numpy(frame0[heavy].copy())))
+    res = cli_oracle_run(mols, 42, steps, 2, MCMC, max_steps, max_batches)
+    res["codes"] = torch.tensor([[ord(c) for c in code] for code in order], dtype=torch.uint8)  # the walkers' labels, in batch order
+    return res
+
+
 CASES = {
+    "oracle_cli_cfg1": lambda max_steps=None, max_batches=None, **kw: cli_cfg1_case(MCMC, 42, 50, max_steps, max_batches),
+    "oracle_cli_cfg1_params": lambda max_steps=None, max_batches=None, **kw: cli_cfg1_case(CLI_PARAMS, CLI_PARAMS_SEED, 12, max_steps, max_batches),
+    "oracle_cli_2aa": lambda max_steps=None, max_batches=None, **kw: cli_2aa_case(12, max_steps, max_batches),
     "oracle_forward_ag4": lambda **kw: forward_case("ag4", True),
     "oracle_forward_chain17x6": lambda **kw: forward_case("chain17x6", True),
     "oracle_forward_ragged": lambda **kw: forward_case("ragged", False),

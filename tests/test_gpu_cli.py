@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import _cli_cases as cc
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,10 +39,35 @@ def test_jamun_sample_cfg1_end_to_end(tmp_path, monkeypatch):
     t = json.load(open(os.path.join(run_dir, "sampler", "timing.json")))
     assert len(t["batches"]) == 2 and t["batches"][0]["conformations"] == 4 * 50
     assert os.path.exists(os.path.join(run_dir, "sampler", "uncapped_AG", "predicted_samples", "pdb", "joined.pdb"))
+    # every file of the run against the CPU oracle of the same command line (tests/golden/oracle_cli_cfg1.npz, fed from synth and the file's bytes)
+    worst = cc.check_run(run_dir, cc.load_fixture("oracle_cli_cfg1"), {"uncapped_AG": (0, 4)}, {"uncapped_AG": cc.ag_molecule()})
+    print(f"\n[cli pin] cfg1: worst per-frame RMSD vs oracle {worst:.3e} nm (bar {cc.RMSD_TOL_NM:.0e})")
     # accelerator=cpu is refused: there is no CPU path
     with pytest.raises(RuntimeError, match="no CPU path"):
         cmdline.main(["--config-dir=" + os.path.join(ROOT, "configs"), "experiment=sample_custom", f"++init_pdbs=[{pdb_path}]",
                       f"++checkpoint_dir={ck_dir}", "checkpoint_type=best_so_far", "num_sampling_steps_per_batch=3", "++trainer.accelerator=cpu"])
+
+
+def test_jamun_sample_cfg1_with_every_parameter_overridden(tmp_path, monkeypatch):
+    """The cfg1 command line with delta, friction, M, inverse_temperature, score_fn_clip and the seed each overridden to a value of its own
+    (`_cli_cases.PARAM_OVERRIDES`; the clip binds on 38 % of the per-atom scores), 2 x 12 steps: every file against
+    tests/golden/oracle_cli_cfg1_params.npz.  In the shipped experiments all of these are 0.04 or 1.0, so a pair exchanged between the yaml
+    and the kernels shows only here."""
+    from jamun_amd import cmdline, pdb, synth
+
+    mol = cc.ag_molecule()
+    pdb_path = str(tmp_path / "uncapped_AG.pdb")
+    pdb.write_pdb(pdb_path, mol, mol["pos"][None])
+    ck_dir = tmp_path / "ckpt"
+    ck_dir.mkdir()
+    torch.save(synth.synthetic_checkpoint(output_gain=0.05, prefix="g._orig_mod."), str(ck_dir / "epoch=7-step=100.ckpt"))
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setenv("JAMUN_ROOT_PATH", str(tmp_path))
+    run_dir = cmdline.main(["--config-dir=" + os.path.join(ROOT, "configs"), "experiment=sample_custom", f"++init_pdbs=[{pdb_path}]",
+                            f"++checkpoint_dir={ck_dir}", "checkpoint_type=best_so_far", "wandb_train_run_path=null", "finetune_on_init=null",
+                            "num_sampling_steps_per_batch=12", "repeat_init_samples=4", "num_batches=2", "++sampler.rng=torch_cpu"] + cc.PARAM_OVERRIDES)
+    worst = cc.check_run(run_dir, cc.load_fixture("oracle_cli_cfg1_params"), {"uncapped_AG": (0, 4)}, {"uncapped_AG": mol})
+    print(f"\n[cli pin] cfg1, every parameter overridden: worst per-frame RMSD vs oracle {worst:.3e} nm (bar {cc.RMSD_TOL_NM:.0e})")
 
 
 def test_jamun_sample_uncapped_2aa_directory_end_to_end(tmp_path, monkeypatch):
@@ -79,13 +106,29 @@ def test_jamun_sample_uncapped_2aa_directory_end_to_end(tmp_path, monkeypatch):
     assert min(sizes.values()) == 9 and max(sizes.values()) == 29
     t = json.load(open(os.path.join(run_dir, "sampler", "timing.json"))) if os.path.exists(os.path.join(run_dir, "sampler", "timing.json")) else None
     assert t is None or t["batches"][0]["conformations"] == len(codes) * 12
+    # every file of all 28 labels against the CPU oracle of the same command line (tests/golden/oracle_cli_2aa.npz: one walker per code,
+    # collated in sorted order, fed from synth.peptide and frame 0 of each `positions` array)
+    assert codes == cc.CODES_2AA
+    fx = cc.load_fixture("oracle_cli_2aa")
+    report = {}
+    worst = cc.check_run(run_dir, fx, cc.labels_2aa(fx), mols, report)
+    print(f"\n[cli pin] 2AA directory: worst per-frame RMSD vs oracle {worst:.3e} nm at {max(report, key=report.get)} (bar {cc.RMSD_TOL_NM:.0e})")
     # max_datasets (data/_utils.py:98-99) through the command line: the first three codes in sorted order, nothing else
     run2 = cmdline.main(args + ["++init_datasets.max_datasets=3", "run_key=second"])
     first = sorted(codes)[:3]
     assert sorted(x for x in os.listdir(os.path.join(run2, "sampler")) if x != "timing.json") == first
+    lab = cc.labels_2aa(fx)
     for c in first:
         b = np.load(os.path.join(run2, "sampler", c, "predicted_samples", "npy", "0.npy"))
         assert b.shape == (sizes[c], 12, 3) and np.isfinite(b).all()
+        # The batch is smaller, so the noise stream is laid out differently and the oracle's numbers do not apply.  What is determined: the
+        # first frame is x-hat of start + sigma * noise, within 6 sigma of the label's own start on every atom, and the files carry the
+        # label's own topology (atom count, names, residues) — labels are not exchanged.
+        start = cc.walker_inputs(fx, lab[c][0])["pos"]
+        assert np.sqrt(((b[:, 0].astype(np.float64) - start) ** 2).sum(-1)).max() <= 6 * cc.SIGMA, c
+        cc.check_topology(run2, c, mols[c], start)
+        names = cc.read_pdb_models(os.path.join(run2, "sampler", c, "predicted_samples", "pdb", "0.pdb"))
+        assert len(names) == 12 and all(m[0] == mols[c]["atom_names"] and m[1] == mols[c]["residues"] for m in names), c
 
 
 _RCCL_WORKER = r'''

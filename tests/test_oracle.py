@@ -249,6 +249,11 @@ def test_cached_oracle_fixtures_are_fresh(golden_dir, tmp_path):
         ("oracle_walk_baoab_ag4_50_mid", {"max_steps": 3}, ["xhat_traj", "y_traj"]),
         ("oracle_walk_aboba_ag4_20", {"max_steps": 3}, ["xhat_traj", "y_traj"]),
         ("oracle_sampler_cc0", {"max_batches": 1}, ["xhat_traj_0"]),
+        # the command-line runs (tests/_cli_cases.py): the inputs the oracle read from the files it wrote, and the first frames
+        ("oracle_cli_cfg1", {"max_steps": 3, "max_batches": 1}, ["pos", "bonds", "atom_code_index", "xhat_traj_0"]),
+        ("oracle_cli_cfg1_params", {"max_steps": 3, "max_batches": 1}, ["xhat_traj_0"]),
+        # (489 atoms: half a minute per oracle forward, so the first frame only — the y0 draw over the whole collated batch)
+        ("oracle_cli_2aa", {"max_steps": 1, "max_batches": 1}, ["pos", "ptr", "codes", "residue_code_index", "xhat_traj_0"]),
     ]
     code = ("import importlib.util, json, sys\nimport numpy as np, torch\ntorch.set_num_threads(1)\n"
             "spec = importlib.util.spec_from_file_location('mk', sys.argv[1]); mk = importlib.util.module_from_spec(spec); spec.loader.exec_module(mk)\n"
