@@ -332,6 +332,48 @@ int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t at
                           const float* clash_s_dev, const int32_t* bonds_dev, const float* bond_lo_s_dev, const float* bond_hi_s_dev,
                           int32_t n_bonds, uint32_t* counts_dev, int64_t counts_capacity, uint32_t* bond_frames_dev, void* stream);
 
+/* ---- TICA of feature trajectories: lagged second moments, projection on fitted components, autocovariance sums -----------------------------
+ * The three reductions over frames behind pyemma's tica(lag, kinetic_map) and statsmodels' acovf as the reference's analysis uses them
+ * (analysis/utils.py: compute_TICA, compute_autocorrelation_stats); the fit itself (two symmetric eigenproblems of size width) is the
+ * host's (jamun_amd/tica.py).  x_dev is fp32 [n_frames] rows of `width` values, row_stride floats apart (what jamun_internal_coords writes
+ * with cossin: row_stride = width); 1 <= width <= 128, row_stride >= width; nothing is read behind the `width` values of a row.
+ *
+ * jamun_lagged_moments: for 1 <= lag < n_frames and the N = n_frames - lag pairs (x_t, x_{t+lag}), t < N, all fp64:
+ *   sums_dev    [2][width]          sum_t x_t, then sum_t x_{t+lag}
+ *   moments_dev [3][width][width]   G = sum_t x_t x_t^T, H = sum_t x_{t+lag} x_{t+lag}^T, K = sum_t x_t x_{t+lag}^T (row = the earlier
+ *                                   frame; not symmetrised)
+ * Every value is promoted to fp64 before it is multiplied, so every product is exact and the only rounding is in the additions: each
+ * output is within gamma_N sum_t |a||b| of the exact sum (gamma_N = N u / (1 - N u), u = 2^-53).  The additions have a fixed order: the
+ * pairs are cut into slices of 1024, a slice's terms are added in ascending t into work_dev [slices][2 width + 3 width^2], and the slices
+ * are added in ascending order; no floating-point atomics.  The same inputs give the same bits in every run, and G and H are symmetric
+ * bit for bit.  Non-finite inputs propagate by IEEE rules.  jamun_lagged_moments_work gives the size of the workspace in doubles
+ * (0 for n_frames == 0); its contents before the call do not matter and mean nothing after it.
+ *
+ * jamun_project_frames: mean_dev fp64 [width], v_dev fp64 [width][d], 1 <= d <= width -> out_dev fp64 [n_frames][d],
+ *   out[t][k] = sum_j (x[t][j] - mean[j]) v[j][k]
+ * the difference formed in fp64, j ascending, one accumulator per output (within gamma_{width+1} sum_j |x - mean||v| of the exact value).
+ * A non-finite x[t][j] makes exactly the d outputs of row t non-finite; every other row is bit for bit what it is without it.
+ *
+ * jamun_autocov_sums: y_dev fp64 [n_frames], `stride` (>= 1) doubles apart (column 0 of a projection is read in place: stride = d),
+ * 0 <= max_lag <= 4096 -> out_dev fp64 [max_lag + 1],
+ *   out[k] = sum_{t < n_frames - k} y_t y_{t+k},   0 for k >= n_frames
+ * in fp64 (within gamma_{n_frames+1} sum_t |y_t y_{t+k}|), in the same fixed order as the moments (slices of 1024 values of t, workspace
+ * [slices][max_lag + 1] doubles, jamun_autocov_sums_work).  The caller divides by n_frames - k: statsmodels' acovf(adjusted=True,
+ * demean=False).  A product is formed only for t + k < n_frames.
+ *
+ * A negative count, stride or capacity, width outside [1, 128], lag outside [1, n_frames), d outside [1, width], max_lag outside [0, 4096],
+ * row_stride < width, stride < 1, work_capacity or out_capacity (in doubles) below the need, or a NULL pointer is JAMUN_ERR_INVALID and
+ * nothing is written; n_frames == 0 launches nothing, writes nothing and succeeds (the ranges of width, d and max_lag are checked first).
+ * Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation. */
+int jamun_lagged_moments_work(int32_t n_frames, int32_t width, int32_t lag, int64_t* n_doubles);
+int jamun_lagged_moments(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, int32_t lag, double* sums_dev, double* moments_dev,
+                         double* work_dev, int64_t work_capacity, void* stream);
+int jamun_project_frames(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, const double* mean_dev, const double* v_dev, int32_t d,
+                         double* out_dev, int64_t out_capacity, void* stream);
+int jamun_autocov_sums_work(int32_t n_frames, int32_t max_lag, int64_t* n_doubles);
+int jamun_autocov_sums(const double* y_dev, int64_t stride, int32_t n_frames, int32_t max_lag, double* out_dev, double* work_dev, int64_t work_capacity,
+                       void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

@@ -544,6 +544,21 @@ class ChemicalValidityMetricsCallback(TrajectoryMetricCallback):
         super().__init__(datasets, functools.partial(ChemicalValidityMetrics, **kw))
 
 
+class TICAMetricsCallback(TrajectoryMetricCallback):
+    """`TrajectoryMetricCallback` over `tica.TICAMetrics` (the slow-mode part of the reference's ``analysis/run_analysis.py``: TICA fitted on
+    the true trajectory, the samples projected on it): per chain and for the joined trajectory the first two components, the
+    Jensen-Shannon distances of their histograms from the true trajectory's and the autocovariance of the first component, under
+    ``<output_dir>/<label>/tica/``.  Keyword arguments go to the meter (``lag``, ``max_acf_lag``, ``features``, ``bins_1d``, ``bins_2d``,
+    ``var_cutoff``, ``epsilon``, ``kinetic_map``, ``reference``, ``device``, ``output_dir``, ``sample_key``)."""
+
+    def __init__(self, datasets: Sequence, **kw):
+        import functools
+
+        from .tica import TICAMetrics
+
+        super().__init__(datasets, functools.partial(TICAMetrics, **kw))
+
+
 class MeasureSamplingTimeCallback:
     """Wall time per batch and per sampled conformation (one saved (walker, frame) pair — the reference's unit,
     ``callbacks/sampler/_measure_sampling_time.py:57,71``).  Writes ``sampler/timing.json`` on rank 0."""

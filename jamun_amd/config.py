@@ -37,6 +37,7 @@ TARGET_ALIASES = {
     "jamun.callbacks.sampler.TrajectoryMetricCallback": "jamun_amd.callbacks.TrajectoryMetricCallback",
     "jamun.callbacks.sampler.RamachandranPlotMetricsCallback": "jamun_amd.callbacks.RamachandranMetricsCallback",
     "jamun.callbacks.sampler.ChemicalValidityMetricsCallback": "jamun_amd.callbacks.ChemicalValidityMetricsCallback",
+    "jamun.callbacks.sampler.TICAMetricsCallback": "jamun_amd.callbacks.TICAMetricsCallback",
     "jamun.sampling.walkjump.MeasurementDependentParametersCallback": "jamun_amd.sampling.MeasurementDependentParametersCallback",
     "jamun.sampling.walkjump.InterpolateParametersCallback": "jamun_amd.sampling.InterpolateParametersCallback",
     "jamun.utils.ModelSamplingWrapper": "jamun_amd.sampling.ModelSamplingWrapper",

@@ -1,6 +1,7 @@
 // jamun_frames.cpp — the C entries that encode or analyse frames of a trajectory and never touch a jamun_sampler: the PDB / DCD encoders
 // (jamun_traj.hip), superposition (jamun_superpose.hip), internal coordinates (jamun_intcoord.hip), histograms of angle pairs with their
-// Jensen-Shannon divergence (jamun_hist.hip) and chemical validity (jamun_validity.hip).  Every refusal is raised before any HIP call.
+// Jensen-Shannon divergence (jamun_hist.hip), chemical validity (jamun_validity.hip) and the reductions behind TICA: lagged moments,
+// projection, autocovariance sums (jamun_tica.hip).  Every refusal is raised before any HIP call.
 // The order of an entry's checks decides which message a caller with two faults sees, and the entries differ in it on purpose: where a
 // shared check below would change an order or a text, the entry keeps a line of its own.  Every entry's checks read top to bottom.
 #include "jamun_host.h"
@@ -32,6 +33,21 @@ void check_bins(int32_t bins) {
 void check_n_cuts(int32_t n_cuts) {
   if (n_cuts < 1 || n_cuts > JAMUN_HIST_MAX_CUTS)
     throw Err(JAMUN_ERR_INVALID, "n_cuts " + std::to_string(n_cuts) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_CUTS) + "]");
+}
+
+void check_tica_width(int32_t width) {
+  if (width < 1 || width > JAMUN_TICA_MAX_WIDTH)
+    throw Err(JAMUN_ERR_INVALID, "width " + std::to_string(width) + " is outside [1, " + std::to_string(JAMUN_TICA_MAX_WIDTH) + "]");
+}
+
+void check_tica_lag(int32_t lag, int32_t n_frames) {
+  if (lag < 1 || lag >= n_frames)
+    throw Err(JAMUN_ERR_INVALID, "lag " + std::to_string(lag) + " is outside [1, n_frames = " + std::to_string(n_frames) + ")");
+}
+
+void check_tica_acf_lag(int32_t max_lag) {
+  if (max_lag < 0 || max_lag > JAMUN_TICA_MAX_ACF_LAG)
+    throw Err(JAMUN_ERR_INVALID, "max_lag " + std::to_string(max_lag) + " is outside [0, " + std::to_string(JAMUN_TICA_MAX_ACF_LAG) + "]");
 }
 
 constexpr int64_t kMaxModel = 1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
@@ -191,6 +207,75 @@ int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t at
     if (bond_frames_dev && n_bonds > 0) HIPCHECK(hipMemsetAsync(bond_frames_dev, 0, (size_t)n_bonds * sizeof(uint32_t), st));
     launch_validity_frames(xyz_dev, frame_stride, atom_stride, n_atoms, n_frames, clash_s_dev, bonds_dev, bond_lo_s_dev, bond_hi_s_dev, n_bonds,
                            counts_dev, bond_frames_dev, st);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- lagged moments, projection and autocovariance sums of feature trajectories (jamun_tica.hip) ----------------------------------------------
+
+int jamun_lagged_moments_work(int32_t n_frames, int32_t width, int32_t lag, int64_t* n_doubles) {
+  return guarded([&] {
+    if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_tica_width(width);
+    if (n_frames == 0) {
+      *n_doubles = 0;
+      return;
+    }
+    check_tica_lag(lag, n_frames);
+    *n_doubles = moments_work_doubles(n_frames, width, lag);
+  });
+}
+
+int jamun_lagged_moments(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, int32_t lag, double* sums_dev, double* moments_dev,
+                         double* work_dev, int64_t work_capacity, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_tica_width(width);
+    if (n_frames == 0) return;  // (nothing to write)
+    check_tica_lag(lag, n_frames);
+    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    require_capacity("work_capacity", work_capacity, moments_work_doubles(n_frames, width, lag), "partial sums", "doubles");
+    if (!x_dev || !sums_dev || !moments_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_lagged_moments(x_dev, row_stride, n_frames, width, lag, sums_dev, moments_dev, work_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_project_frames(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, const double* mean_dev, const double* v_dev, int32_t d,
+                         double* out_dev, int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0 || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_tica_width(width);
+    if (d < 1 || d > width) throw Err(JAMUN_ERR_INVALID, "d " + std::to_string(d) + " is outside [1, width = " + std::to_string(width) + "]");
+    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    require_capacity("out_capacity", out_capacity, (int64_t)n_frames * d, "projections", "doubles");
+    if (n_frames == 0) return;  // (nothing to write)
+    if (!x_dev || !mean_dev || !v_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_project_frames(x_dev, row_stride, n_frames, width, mean_dev, v_dev, d, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_autocov_sums_work(int32_t n_frames, int32_t max_lag, int64_t* n_doubles) {
+  return guarded([&] {
+    if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_tica_acf_lag(max_lag);
+    *n_doubles = n_frames == 0 ? 0 : autocov_work_doubles(n_frames, max_lag);
+  });
+}
+
+int jamun_autocov_sums(const double* y_dev, int64_t stride, int32_t n_frames, int32_t max_lag, double* out_dev, double* work_dev, int64_t work_capacity,
+                       void* stream) {
+  return guarded([&] {
+    if (stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_tica_acf_lag(max_lag);
+    if (n_frames == 0) return;  // (nothing to write)
+    if (stride < 1) throw Err(JAMUN_ERR_INVALID, "stride 0: the values of y must lie apart");
+    require_capacity("work_capacity", work_capacity, autocov_work_doubles(n_frames, max_lag), "partial sums", "doubles");
+    if (!y_dev || !out_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_autocov_sums(y_dev, stride, n_frames, max_lag, out_dev, work_dev, (hipStream_t)stream);
     HIPCHECK(hipGetLastError());
   });
 }

@@ -533,3 +533,16 @@ void launch_js_divergence(const unsigned* counts, int n_cuts, int n_pairs, int b
 void launch_validity_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* clash_s,
                             const int* bonds, const float* bond_lo_s, const float* bond_hi_s, int n_bonds, unsigned* counts,
                             unsigned* bond_frames, hipStream_t st);
+// jamun_tica.hip — lagged second moments of a feature trajectory, its projection on fitted components, autocovariance sums: reductions over
+// frames in a fixed order (partials per slice of frames in the caller's workspace, then one pass in slice order); n_frames >= 1
+#define JAMUN_TICA_MAX_WIDTH 128     // feature columns the moments and the projection take (native.TICA_MAX_WIDTH mirrors it)
+#define JAMUN_TICA_MAX_ACF_LAG 4096  // largest lag of the autocovariance sums (native.TICA_MAX_ACF_LAG)
+#define JAMUN_TICA_SLICE 1024        // frames (lag pairs) whose terms one workgroup adds: the unit of the workspace (native.TICA_SLICE, for the tests)
+#define JAMUN_TICA_TILE 32           // rows and columns of the moment matrices a workgroup owns (native.TICA_TILE, for the tests)
+long long moments_work_doubles(int n_frames, int width, int lag);  // (1 <= lag < n_frames)
+long long autocov_work_doubles(int n_frames, int max_lag);
+void launch_lagged_moments(const float* x, long long row_stride, int n_frames, int width, int lag, double* sums, double* moments, double* work,
+                           hipStream_t st);
+void launch_project_frames(const float* x, long long row_stride, int n_frames, int width, const double* mean, const double* v, int d, double* out,
+                           hipStream_t st);
+void launch_autocov_sums(const double* y, long long stride, int n_frames, int max_lag, double* out, double* work, hipStream_t st);

@@ -818,3 +818,128 @@ def validity_counts(frames: torch.Tensor, tables, out: Optional[torch.Tensor] = 
         _lib.check(lib.jamun_validity_counts(_ptr(frames), fs, as_, n, T, _ptr(t["clash_s"]), _ptr(t["bonds"]), _ptr(t["bond_lo_s"]), _ptr(t["bond_hi_s"]),
                                              B, _ptr(out), int(out.numel()), _ptr(bond_frames), _stream()))
     return out, bond_frames
+
+
+# ---- lagged moments, projection and autocovariance sums of feature trajectories (jamun_tica.hip) -------------------------------------------
+
+TICA_MAX_WIDTH = 128     # feature columns the moments and the projection take (JAMUN_TICA_MAX_WIDTH, jamun_internal.h)
+TICA_MAX_ACF_LAG = 4096  # largest lag of the autocovariance sums (JAMUN_TICA_MAX_ACF_LAG)
+TICA_SLICE = 1024        # frames whose terms one workgroup adds (JAMUN_TICA_SLICE)
+TICA_TILE = 32           # rows and columns of the moment matrices a workgroup owns (JAMUN_TICA_TILE)
+
+_tica_work: Dict[Tuple[str, int], torch.Tensor] = {}  # (device, stream) -> the workspace of the two-pass reductions, grown on demand
+
+
+def _tica_workspace(device, n_doubles: int) -> torch.Tensor:
+    """The workspace of `lagged_moments` / `autocov_sums` on the current stream of ``device``: one per (device, stream), since the calls
+    of one stream run one after the other and those of two streams may not share partial sums."""
+    key = (str(device), _stream())
+    have = _tica_work.get(key)
+    if have is None or have.numel() < n_doubles:
+        have = _tica_work[key] = torch.empty(max(int(n_doubles), 1), dtype=torch.float64, device=device)
+    return have
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def check_feature_rows(x) -> Tuple[int, int]:
+    """The shape rule of the feature rows `lagged_moments` and `project_frames` read, before anything needs a GPU: a ``[T, W]`` tensor
+    with ``1 <= W <= 128`` (``ValueError`` otherwise).  Returns ``(T, W)``."""
+    if not torch.is_tensor(x) or x.ndim != 2:
+        raise ValueError(f"x must be a [frames, width] tensor, got {tuple(getattr(x, 'shape', ()))}")
+    T, W = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= W <= TICA_MAX_WIDTH:
+        raise ValueError(f"{W} feature columns: the device path takes 1 to {TICA_MAX_WIDTH} (tica.lagged_moments_host has no limit)")
+    return T, W
+
+
+def _feature_rows(x: torch.Tensor, T: int, W: int) -> int:
+    """``RuntimeError`` unless ``x`` is float32 on a GPU with adjacent columns; returns the row stride in floats."""
+    if not x.is_cuda or x.dtype != torch.float32 or (W > 1 and x.stride(1) != 1) or (T > 1 and x.stride(0) < W):
+        raise RuntimeError(f"x must be a float32 tensor on the GPU with adjacent columns, got {x.dtype} {tuple(x.shape)} strides {tuple(x.stride())} "
+                           f"on {x.device}")
+    _fit_31_bits(f"{T} frames: the count must fit 31 bits", T)
+    return int(x.stride(0)) if T > 1 else W
+
+
+def lagged_moments(x: torch.Tensor, lag: int, sums: Optional[torch.Tensor] = None,
+                   moments: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Queue the lagged second moments of the feature rows ``x [T, W]`` (device fp32 with adjacent columns: what `internal_coords` returns
+    with ``cossin``, or a view of it with a row stride) on the current stream: ``(sums float64 [2, W], moments float64 [3, W, W])`` over
+    the ``T - lag`` pairs ``(x_t, x_{t+lag})``: the sums of ``x_t`` and of ``x_{t+lag}``, and ``G``, ``H``, ``K`` as
+    `tica.lagged_moments_host` defines them.  ``1 <= lag < T`` and ``1 <= W <= 128`` (``ValueError`` otherwise, before anything needs a
+    GPU).  ``sums`` / ``moments`` (contiguous float64 of those shapes on the device) receive the result; default new tensors.  The
+    workspace is this module's.  Same inputs, same bits.  See ``jamun_lagged_moments``."""
+    T, W = check_feature_rows(x)
+    if not _is_int(lag) or not 1 <= int(lag) < T:
+        raise ValueError(f"lag must be an integer in [1, {T}) for {T} frames, got {lag!r}")
+    lag = int(lag)
+    row_stride = _feature_rows(x, T, W)
+    lib = _lib.load()
+    dev = x.device
+    sums = _result("sums", sums, (2, W), torch.float64, dev)
+    moments = _result("moments", moments, (3, W, W), torch.float64, dev)
+    need = C.c_int64()
+    _lib.check(lib.jamun_lagged_moments_work(T, W, lag, C.byref(need)))
+    with torch.cuda.device(dev):
+        work = _tica_workspace(dev, need.value)
+        _lib.check(lib.jamun_lagged_moments(_ptr(x), row_stride, T, W, lag, _ptr(sums), _ptr(moments), _ptr(work), int(work.numel()), _stream()))
+    return sums, moments
+
+
+def project_frames(x: torch.Tensor, mean, v, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the projection of the feature rows ``x [T, W]`` (as `lagged_moments` takes them) on the current stream: float64 ``[T, d]``,
+    ``out[t] = (x[t] - mean) @ v`` with ``mean [W]`` and ``v [W, d]``, ``1 <= d <= W`` (float64; host arrays are uploaded, tensors on the
+    device of ``x`` are used as they are).  ``out`` (contiguous float64 ``[T, d]`` on the device) receives the result; default a new
+    tensor.  `tica.project_host` is the specification.  See ``jamun_project_frames``."""
+    T, W = check_feature_rows(x)
+    shape_v = tuple(getattr(v, "shape", ()))
+    if tuple(getattr(mean, "shape", ())) != (W,) or len(shape_v) != 2 or shape_v[0] != W or not 1 <= shape_v[1] <= W:
+        raise ValueError(f"mean must have shape [{W}] and v [{W}, d] with 1 <= d <= {W}, got {tuple(getattr(mean, 'shape', ()))} and {shape_v}")
+    d = int(shape_v[1])
+    row_stride = _feature_rows(x, T, W)
+    lib = _lib.load()
+    dev = x.device
+
+    def f64(a, what):
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        if a.dtype != torch.float64:
+            raise ValueError(f"{what} must hold float64, got {a.dtype}")
+        return a.to(dev).contiguous()
+
+    mean, v = f64(mean, "mean"), f64(v, "v")
+    out = _result("out", out, (T, d), torch.float64, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_project_frames(_ptr(x), row_stride, T, W, _ptr(mean), _ptr(v), d, _ptr(out), int(out.numel()), _stream()))
+    return out
+
+
+def autocov_sums(y: torch.Tensor, max_lag: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the autocovariance sums of ``y [T]`` (device float64, any positive stride: a column of `project_frames`' result is read in
+    place) on the current stream: float64 ``[max_lag + 1]``, ``out[k] = sum_{t < T - k} y[t] y[t + k]`` and 0 for ``k >= T``;
+    ``0 <= max_lag <= 4096`` (``ValueError`` otherwise).  Dividing by ``T - k`` gives statsmodels' ``acovf(adjusted=True, demean=False)``.
+    ``out`` (contiguous float64 of that shape on the device) receives the result; default a new tensor.  The workspace is this module's.
+    Same inputs, same bits.  `tica.autocov_sums_host` is the specification.  See ``jamun_autocov_sums``."""
+    if not torch.is_tensor(y) or y.ndim != 1:
+        raise ValueError(f"y must be a [frames] tensor, got {tuple(getattr(y, 'shape', ()))}")
+    if not _is_int(max_lag) or not 0 <= int(max_lag) <= TICA_MAX_ACF_LAG:
+        raise ValueError(f"max_lag must be an integer in [0, {TICA_MAX_ACF_LAG}], got {max_lag!r}")
+    max_lag, T = int(max_lag), int(y.shape[0])
+    if not y.is_cuda or y.dtype != torch.float64 or (T > 1 and y.stride(0) < 1):
+        raise RuntimeError(f"y must be a float64 tensor on the GPU with a positive stride, got {y.dtype} {tuple(y.shape)} strides {tuple(y.stride())} "
+                           f"on {y.device}")
+    _fit_31_bits(f"{T} frames: the count must fit 31 bits", T)
+    lib = _lib.load()
+    dev = y.device
+    out = _result("out", out, (max_lag + 1,), torch.float64, dev)
+    need = C.c_int64()
+    _lib.check(lib.jamun_autocov_sums_work(T, max_lag, C.byref(need)))
+    with torch.cuda.device(dev):
+        if T == 0:
+            out.zero_()  # (no frame: the call writes nothing)
+        work = _tica_workspace(dev, need.value)
+        _lib.check(lib.jamun_autocov_sums(_ptr(y), int(y.stride(0)) if T > 1 else 1, T, max_lag, _ptr(out), _ptr(work), int(work.numel()), _stream()))
+    return out
