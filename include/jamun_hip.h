@@ -484,6 +484,20 @@ int jamun_debug_read(jamun_sampler* s, int32_t what, int32_t layer, float* out_d
 int jamun_debug_plan_segments(int32_t cus, int32_t ng, int32_t n_k, int32_t n_atoms, int32_t n_tiles, const int32_t* tile_atoms,
                               const int32_t* tile_chunk, int32_t n_chunks, const int64_t* tile_weight, const int8_t* skip, double seg_cost,
                               int32_t* segs_out, int64_t segs_capacity, int32_t* max_segs, int32_t* n_slabs, int32_t* atom_nslab);
+/* Host only, no device calls: the kernel selection of jamun_sampler_create (tile plan, hidden-layer kernel, tail tiles, work lists, initial
+ * projector) for a model's hyper-parameters, tuning switches (NULL: defaults) and topology on a device with `cus` compute units, with
+ * n_uniq distinct embedding rows and what packing produced given by the caller: hidden [n_hidden] per hidden layer bit 0 / 1 / 2 = its
+ * weights for k_conv_dg / the matrix-formed kernels / the tail tiles are present; layer0 [5] = {k_conv_init_v table, k_conv_mfi table, its
+ * selector tiles (1, 2, 4), k_conv_mfx weights, 32-column tiles of the scalar outputs} of the initial projector.
+ * out24 = {conv_path, dg_mode, init_path, dg_emu, dg_RS, edge stride S, n_tiles, span_max, row_blocks, n_tail_tiles, n_tail, tail_runs,
+ *          init_tail, own_init_segs, mf_nks, ml_window, initv_nbuf, ng, seg_cost_tenths, max_segs, n_slabs, conv_flop_exec_launch,
+ *          max_segs, n_slabs of the initial projector's own lists}, the enumerations as jamun_stats documents them (SeparableConv: -1) and
+ * as the plan holds them (dg_mode 0 and mf_nks 4 also where no destination-grouped kernel runs).
+ * which = -1: no list; 0..5 as jamun_debug_segments (records without the tile descriptor), 6: destination chunk per tile.  list_len
+ * receives the list's int32 values; list may be NULL, else capacity >= list_len. */
+int jamun_debug_select_kernels(const jamun_hparams* hp, const jamun_tuning* tuning, const jamun_topology* topo, int32_t cus, int32_t n_uniq,
+                               int32_t have_atom_uid, int32_t n_hidden, const int32_t* hidden, const int32_t* layer0, int64_t* out24,
+                               int32_t which, int32_t* list, int64_t capacity, int64_t* list_len);
 /* The lists a sampler's kernels run, copied to the host (synchronous; the sampler needs a destination-grouped plan):
  *   which = 0: hidden layers' segment records (the second record carries the tile descriptor {k_extra, first atom, atoms | rows << 8, first row})
  *           1: the initial projector's own records (none when it runs list 0)     2: tail-tile records [n_tail_tiles] int4

@@ -145,6 +145,8 @@ SYMBOLS = {
     "jamun_debug_read": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P]),
     "jamun_debug_plan_segments": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_double,
                                             _P, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "jamun_debug_select_kernels": (C.c_int, [C.POINTER(jamun_hparams), C.POINTER(jamun_tuning), C.POINTER(jamun_topology), C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "jamun_debug_segments": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     "jamun_debug_live_allocations": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }

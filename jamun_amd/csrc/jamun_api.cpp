@@ -34,7 +34,7 @@ struct ProfScope {
 // Radial MLPs' hidden activations (k_edge_h; they depend on the geometry only) of n_layers blocks from block l0 on
 void edge_h(jamun_sampler* s, size_t l0, int n_layers, hipStream_t st) {
   ProfScope ps(s, JAMUN_PROF_EDGE_H, st);
-  if (s->conv_path != CONV_WIDE) {
+  if (s->plan.conv_path != CONV_WIDE) {
     launch_edge_h(s->deg, s->esrc, s->egeo, s->n_atoms, s->S, s->w1r_all + l0 * 64 * 32, s->cmask_all + l0 * 128, n_layers, s->mu, s->rb_step, s->h,
                   s->h_stride, s->h_kstride, st, s->w1h_all ? s->w1h_all + l0 * 8 * 64 : nullptr, s->w1isc_all ? s->w1isc_all + l0 : nullptr);
     return;
@@ -72,7 +72,7 @@ A edge_args(const jamun_sampler* s, const float* h_l) {
 template <typename A>
 A tile_args(const jamun_sampler* s, const LayerDev& L, const float* h_l) {
   A a = edge_args<A>(s, h_l);
-  a.n_pad = s->n_pad; a.nt0 = L.p0.nt; a.tile_span = s->dg_tile_span; a.tile_atoms = s->dg_tile_atoms;
+  a.n_pad = s->n_pad; a.nt0 = L.p0.nt; a.tile_span = s->dev.tile_span; a.tile_atoms = s->dev.tile_atoms;
   a.partial0 = s->partial0; a.partial1 = s->partial1;
   return a;
 }
@@ -83,22 +83,22 @@ A mf_args(const jamun_sampler* s, const LayerDev& L, const float* h_l) {
   int e3 = 0;
   std::frexp(1.5 * (double)L.dg.hmax2, &e3);  // 3 max|h~| < 2^e3
   a.sC = std::max(-40, std::min(40, 14 - e3));
-  a.epair = s->epair; a.err = s->mf_err;
+  a.epair = s->epair; a.err = s->dev.mf_err;
   return a;
 }
 // The work lists and slab counts of a layer on the tile plan: the initial projector's own lists when it keeps the tail tiles (init_segs),
 // else the hidden layers'
 struct SegLists { const int4* segs; int max_segs; const int* atom_nslab; int n_slabs; };
 SegLists seg_lists(const jamun_sampler* s, bool initial) {
-  if (initial && s->init_segs) return {s->init_segs, s->init_max_segs, s->init_atom_nslab, s->init_n_slabs};
-  return {s->dg_segs, s->dg_max_segs, s->dg_atom_nslab, s->dg_n_slabs};
+  if (initial && s->plan.own_init_segs) return {s->dev.init_segs, s->plan.init_segs.max_segs, s->dev.init_atom_nslab, s->plan.init_segs.n_slabs};
+  return {s->dev.segs, s->plan.segs.max_segs, s->dev.atom_nslab, s->plan.segs.n_slabs};
 }
 // Tail tiles (k_tail_form* + k_tail_contract): the fields the hidden layers and the initial projector share; each adds its operands
 TailArgs tail_args(const jamun_sampler* s, const LayerDev& L, const float* h_l) {
   TailArgs t = mf_args<TailArgs>(s, L, h_l);
-  t.n_k = s->hp.edge_attr_dim + 1; t.tail_tiles = s->tail_tiles;
-  t.n_tail_tiles = s->n_tail_tiles; t.n_tail = s->n_tail; t.n_runs = s->tail_runs; t.tail_atom = s->tail_atom; t.tail_scale = s->tail_scale;
-  t.P = s->tail_P;
+  t.n_k = s->hp.edge_attr_dim + 1; t.tail_tiles = s->dev.tail_tiles;
+  t.n_tail_tiles = s->plan.n_tail_tiles(); t.n_tail = s->plan.n_tail(); t.n_runs = s->plan.tail_runs; t.tail_atom = s->dev.tail_atom; t.tail_scale = s->dev.tail_scale;
+  t.P = s->dev.tail_P;
   return t;
 }
 // the initial projector's operands formed from the feature rows (k_conv_mfx, k_conv_mlx)
@@ -114,8 +114,8 @@ A init_x_args(const jamun_sampler* s, const LayerDev& L, const float* h_l) {
 template <typename A>
 A hidden_mf_args(const jamun_sampler* s, const LayerDev& L, const float* h_l, const float* x_in, int XSin) {
   A f = mf_args<A>(s, L, h_l);
-  f.x = x_in; f.XS = XSin; f.n_atoms = s->n_atoms; f.segs = s->dg_segs; f.max_segs = s->dg_max_segs;
-  f.wm = L.dg.wm; f.Tt = s->dg_T; f.t_stride = s->dg_tstride; f.sB = L.dg.sB; f.sTw = L.dg.sTw;
+  f.x = x_in; f.XS = XSin; f.n_atoms = s->n_atoms; f.segs = s->dev.segs; f.max_segs = s->plan.segs.max_segs;
+  f.wm = L.dg.wm; f.Tt = s->dev.T; f.t_stride = s->dev.tstride; f.sB = L.dg.sB; f.sTw = L.dg.sTw;
   f.gx = L.dg.gx; f.cf0 = L.dg.cf0; f.cf1 = L.dg.cf1; f.x1 = s->x1;
   return f;
 }
@@ -127,10 +127,10 @@ void check_launch(int rcode, const char* what) {
 // ---- the conv of one block, by kernel family -------------------------------------------------------
 // k_conv / k_conv_wide: one launch for the scalar rows, one for the vector rows
 void conv_general(jamun_sampler* s, size_t l, const float* h_l, const float* x_in, int XSin, hipStream_t st) {
-  const bool wide = s->conv_path == CONV_WIDE;
+  const bool wide = s->plan.conv_path == CONV_WIDE;
   LayerDev& L = s->layers[l];
   ConvArgs a = edge_args<ConvArgs>(s, h_l);
-  a.x = x_in; a.n_atoms = s->n_atoms; a.n_pad = s->n_pad; a.n_tiles = s->n_tiles; a.S4 = (s->S + 3) & ~3; a.XS = XSin;
+  a.x = x_in; a.n_atoms = s->n_atoms; a.n_pad = s->n_pad; a.n_tiles = s->n_pad / 32; a.S4 = (s->S + 3) & ~3; a.XS = XSin;
   a.n_slices = s->n_slices;
   for (int pi = 0; pi < 2; ++pi) {
     ConvProblemDev& P = pi == 0 ? L.p0 : L.p1;
@@ -165,37 +165,37 @@ void conv_init_tiles(jamun_sampler* s, const float* h_l, hipStream_t st) {
   const SegLists sl = seg_lists(s, true);
   {
     ProfScope ps(s, JAMUN_PROF_CONV0_INIT, st);
-    switch (s->init_path) {
+    switch (s->plan.init_path) {
       case INIT_MFI: {
         MfiArgs f = mf_args<MfiArgs>(s, L, h_l);
         f.segs = sl.segs; f.max_segs = sl.max_segs;
         f.atom_uid = s->atom_uid; f.tabw = L.tabw; f.sB = L.tab_sB; f.ut = L.tab_ut;
-        check_launch(launch_conv_mfi(f, s->dg_grid, st), failed);
+        check_launch(launch_conv_mfi(f, s->cus, st), failed);
         break;
       }
       case INIT_MFX: {
         const MfxArgs f = init_x_args<MfxArgs>(s, L, h_l);
-        check_launch(launch_conv_mfx(f, s->dg_grid, st), failed);
+        check_launch(launch_conv_mfx(f, s->cus, st), failed);
         break;
       }
       case INIT_MLX: {
         MlxArgs f = init_x_args<MlxArgs>(s, L, h_l);
-        f.window = s->ml_window; f.mfma_count = nullptr;
-        check_launch(launch_conv_mlx(f, s->dg_grid, st), failed);
+        f.window = s->plan.ml_window; f.mfma_count = nullptr;
+        check_launch(launch_conv_mlx(f, s->cus, st), failed);
         break;
       }
       default: {  // INIT_V
         InitVArgs f = tile_args<InitVArgs>(s, L, h_l);
-        f.PMAX = (s->S + 3) & ~3; f.RS = s->dg_RS; f.nbuf = s->initv_nbuf;
+        f.PMAX = (s->S + 3) & ~3; f.RS = s->plan.dg_RS; f.nbuf = s->plan.initv_nbuf;
         f.segs = sl.segs; f.max_segs = sl.max_segs;
         f.atom_uid = s->atom_uid; f.tt2 = L.tt2; f.tt2_kstride = (size_t)L.tt_U * 192;
         f.dbg = 0;
-        check_launch(launch_conv_initv(f, s->dg_grid, st), failed);
+        check_launch(launch_conv_initv(f, s->cus, st), failed);
         break;
       }
     }
   }
-  if (s->init_tail) {  // (INIT_MFI / INIT_MFX only: the tail tiles through k_tail_form_init / k_tail_contract)
+  if (s->plan.init_tail) {  // (INIT_MFI / INIT_MFX only: the tail tiles through k_tail_form_init / k_tail_contract)
     TailArgs t = tail_args(s, L, h_l);
     t.xph = L.xph; t.xpl = L.xpl; t.wx = L.wx; t.sX = L.x_sX; t.cf0 = L.xcf0; t.cf1t = L.xcf1;
     ProfScope pt(s, JAMUN_PROF_CONV1_INIT, st);
@@ -206,43 +206,43 @@ void conv_init_tiles(jamun_sampler* s, const float* h_l, hipStream_t st) {
 // A hidden layer on the tile plan (CONV_DG): the T pre-pass, then k_conv_mf (+ tail tiles), k_conv_ml or k_conv_dg by dg_mode
 void conv_hidden_tiles(jamun_sampler* s, size_t l, const float* h_l, const float* x_in, int XSin, hipStream_t st) {
   LayerDev& L = s->layers[l];
-  const bool mf = s->dg_mode == 4 || s->dg_mode == 5;
+  const bool mf = matrix_formed(s->plan.dg_mode);
   {
     ProfScope pt(s, JAMUN_PROF_TPROD, st);
-    if (mf) launch_tprod(x_in, XSin, s->n_atoms, s->hp.edge_attr_dim + 1, L.dg.wt, L.dg.wth, L.dg.gT, L.dg.cfT, s->dg_T, s->dg_tstride, st, s->tune.no_tprod_t != 0);
-    else launch_tprod(x_in, XSin, s->n_atoms, s->hp.edge_attr_dim + 1, L.dg.wt, s->dg_emu ? L.dg.wth : nullptr, L.dg.gT, L.dg.cfT, s->dg_T, 0, st);
+    if (mf) launch_tprod(x_in, XSin, s->n_atoms, s->hp.edge_attr_dim + 1, L.dg.wt, L.dg.wth, L.dg.gT, L.dg.cfT, s->dev.T, s->dev.tstride, st, s->tune.no_tprod_t != 0);
+    else launch_tprod(x_in, XSin, s->n_atoms, s->hp.edge_attr_dim + 1, L.dg.wt, s->plan.dg_emu ? L.dg.wth : nullptr, L.dg.gT, L.dg.cfT, s->dev.T, 0, st);
   }
-  if (s->dg_mode == 4) {
+  if (s->plan.dg_mode == DG_MF) {
     MfArgs f = hidden_mf_args<MfArgs>(s, L, h_l, x_in, XSin);
-    f.nks = s->mf_nks;
+    f.nks = s->plan.mf_nks;
     {
       ProfScope ps(s, JAMUN_PROF_CONV0, st);
-      check_launch(launch_conv_mf(f, s->dg_grid, st), "matrix-formed conv launch failed (configuration not supported)");
+      check_launch(launch_conv_mf(f, s->cus, st), "matrix-formed conv launch failed (configuration not supported)");
     }
-    if (s->n_tail_tiles) {
+    if (s->plan.n_tail_tiles()) {
       TailArgs t = tail_args(s, L, h_l);
       t.x = x_in; t.XS = XSin; t.gx = L.dg.gx; t.wm = L.dg.wm; t.wmt = L.dg.wmt; t.cf0 = L.dg.cf0; t.cf1t = L.dg.cf1t;
       ProfScope pt(s, JAMUN_PROF_CONV1, st);
       check_launch(launch_conv_tail(t, st), "tail-tile conv launch failed (configuration not supported)");
     }
-  } else if (s->dg_mode == 5) {
+  } else if (s->plan.dg_mode == DG_ML) {
     MlArgs f = hidden_mf_args<MlArgs>(s, L, h_l, x_in, XSin);
-    f.window = s->ml_window; f.mfma_count = s->ml_count;
+    f.window = s->plan.ml_window; f.mfma_count = s->dev.ml_count;
     ProfScope ps(s, JAMUN_PROF_CONV0, st);
-    check_launch(launch_conv_ml(f, s->dg_grid, st), "large-span matrix-formed conv launch failed (configuration not supported)");
+    check_launch(launch_conv_ml(f, s->cus, st), "large-span matrix-formed conv launch failed (configuration not supported)");
     ++s->ml_launches;
   } else {
     DgArgs f = tile_args<DgArgs>(s, L, h_l);
-    f.x = x_in; f.XS = XSin; f.RS = s->dg_RS; f.PMAX = (s->S + 3) & ~3;  // multiple of the forming batch
-    f.segs = s->dg_segs; f.max_segs = s->dg_max_segs;
-    f.row_blocks = s->dg_row_blocks ? 1 : 0; f.alt = s->dg_mode;
-    f.wx = L.dg.wx; f.wd = L.dg.wd; f.wv = L.dg.wv; f.T = s->dg_T; f.n_atoms = s->n_atoms;
-    f.emu = s->dg_emu; f.wh = L.dg.wxh; f.sB = L.dg.sB; f.hmax2 = L.dg.hmax2;
+    f.x = x_in; f.XS = XSin; f.RS = s->plan.dg_RS; f.PMAX = (s->S + 3) & ~3;  // multiple of the forming batch
+    f.segs = s->dev.segs; f.max_segs = s->plan.segs.max_segs;
+    f.row_blocks = s->plan.tiles.row_blocks ? 1 : 0; f.alt = s->plan.dg_mode;
+    f.wx = L.dg.wx; f.wd = L.dg.wd; f.wv = L.dg.wv; f.T = s->dev.T; f.n_atoms = s->n_atoms;
+    f.emu = s->plan.dg_emu; f.wh = L.dg.wxh; f.sB = L.dg.sB; f.hmax2 = L.dg.hmax2;
     f.gx = L.dg.gx; f.cf0 = L.dg.cf0; f.cf1 = L.dg.cf1;
     f.dbg = 0;
     f.dump = nullptr;
     ProfScope ps(s, JAMUN_PROF_CONV0, st);
-    check_launch(launch_conv_dg(f, s->dg_grid, st), "destination-grouped conv launch failed (configuration not supported)");
+    check_launch(launch_conv_dg(f, s->cus, st), "destination-grouped conv launch failed (configuration not supported)");
   }
 }
 
@@ -257,7 +257,7 @@ void node_update(jamun_sampler* s, size_t l, bool on_tiles, const float* x_in, i
     n.mul0 = s->hp.mul0; n.mul1 = s->hp.mul1; n.in0 = L.in0; n.in1 = L.in1; n.XSin = XSin;
     return n;
   };
-  if (s->conv_path == CONV_WIDE) {
+  if (s->plan.conv_path == CONV_WIDE) {
     NodeWideArgs n = common(NodeWideArgs{});
     n.z0 = s->z0; n.z1 = s->z1; n.wn0 = L.wn0; n.wn1 = L.wn1; n.K0p = L.K0w; n.K1p = L.K1w;
     n.no0 = (s->hp.mul0 + 31) / 32; n.no1 = (s->hp.mul1 + 31) / 32;
@@ -271,7 +271,7 @@ void node_update(jamun_sampler* s, size_t l, bool on_tiles, const float* x_in, i
     const SegLists sl = seg_lists(s, l == 0);
     n.atom_nslab = sl.atom_nslab; n.max_slabs = sl.n_slabs;
   }
-  if (s->conv_path == CONV_SEP) { n.n_slices = 1; n.max_slabs = 1; }  // SeparableConv writes the summed messages as ONE slab
+  if (s->plan.conv_path == CONV_SEP) { n.n_slices = 1; n.max_slabs = 1; }  // SeparableConv writes the summed messages as ONE slab
   n.wh0 = L.wh0; n.wh1 = L.wh1; n.K0h = L.K0h; n.K1h = L.K1h;
   n.kga0 = L.kga0; n.kga1 = L.kga1; n.kgx = L.kgx; n.cg0 = L.cg0; n.cg1 = L.cg1;
   if (!s->tune.node_fp32 && node_update_h_supported(n)) launch_node_update_h(n, s->cus, st);  // (node_fp32: the v_mfma_f32_32x32x2_f32 kernel, A/B aid)
@@ -285,13 +285,13 @@ void run_layer(jamun_sampler* s, size_t l, const float* x_in, int XSin, float* x
   if (!s->h_batched) edge_h(s, l, 1, st);  // (batches above 4 GiB of activations: one layer's radial MLP at a time)
   bool on_tiles = false;  // the conv ran on the tile plan: its slabs are the plan's, not the n_slices K-slices
   if (l == 0) {
-    switch (s->init_path) {
+    switch (s->plan.init_path) {
       case INIT_V: case INIT_MFI: case INIT_MFX: case INIT_MLX: conv_init_tiles(s, h_l, st); on_tiles = true; break;
       case INIT_SEP: conv_separable(s, l, h_l, x_in, XSin, st); break;
       case INIT_GENERAL: case INIT_WIDE: conv_general(s, l, h_l, x_in, XSin, st); break;
     }
   } else {
-    switch (s->conv_path) {
+    switch (s->plan.conv_path) {
       case CONV_DG: conv_hidden_tiles(s, l, h_l, x_in, XSin, st); on_tiles = true; break;
       case CONV_SEP: conv_separable(s, l, h_l, x_in, XSin, st); break;
       case CONV_GENERAL: case CONV_WIDE: conv_general(s, l, h_l, x_in, XSin, st); break;
@@ -306,13 +306,13 @@ void run_layer(jamun_sampler* s, size_t l, const float* x_in, int XSin, float* x
 // at that word, so a disagreement between plan and kernel surfaces as JAMUN_ERR_INVALID at the next call after the copy landed —
 // at the latest in jamun_sampler_stats, which synchronises — instead of as silently wrong coordinates.
 void mf_err_check(jamun_sampler* s) {
-  if (s->mf_err_host && *(volatile int*)s->mf_err_host != 0)
-    throw Err(JAMUN_ERR_INVALID, (*(volatile int*)s->mf_err_host & 2)
+  if (s->dev.mf_err_host && *(volatile int*)s->dev.mf_err_host != 0)
+    throw Err(JAMUN_ERR_INVALID, (*(volatile int*)s->dev.mf_err_host & 2)
                                      ? "k_conv_mf: an edge's source lies outside the rows the selected instantiation multiplies (host plan and kernel disagree) — results of this sampler are invalid"
                                      : "k_conv_mf: more than three edges of one (source, destination) pair — results of this sampler are invalid");
 }
 void mf_err_fetch(jamun_sampler* s, hipStream_t st) {
-  if (s->mf_err && s->mf_err_host) HIPCHECK(hipMemcpyAsync(s->mf_err_host, s->mf_err, sizeof(int), hipMemcpyDeviceToHost, st));
+  if (s->dev.mf_err && s->dev.mf_err_host) HIPCHECK(hipMemcpyAsync(s->dev.mf_err_host, s->dev.mf_err, sizeof(int), hipMemcpyDeviceToHost, st));
 }
 
 // One denoiser forward.  `pre` / `post`: the two halves of a BAOAB iteration fused into the first and the last kernel of the
@@ -332,7 +332,7 @@ void forward(jamun_sampler* s, float* y, float* xhat, float* score, hipStream_t 
   hd.cS = s->hp.act_gate_const; hd.n_atoms = s->n_atoms; hd.mul0 = s->hp.mul0; hd.mul1 = s->hp.mul1;
   {
     ProfScope ps(s, JAMUN_PROF_HEAD, st);
-    if (s->conv_path == CONV_WIDE) launch_head_wide(hd, st);
+    if (s->plan.conv_path == CONV_WIDE) launch_head_wide(hd, st);
     else launch_head(hd, st);
     if (next_pre)  // walk: this iteration's finalize and the next iteration's geometry in one launch
       launch_finalize_geom(y, s->yc, s->g, s->ptr, s->n_graphs, s->c_skip, s->c_out, s->sigma * s->sigma, s->hp.mean_center, s->tmp, xhat, score, post,
@@ -370,50 +370,47 @@ bool saves(const jamun_mcmc_params* p, int i) { return (i % p->save_every_n_step
 // ---- FLOP and byte model: what create fixes per sampler (count_flops) and what needs the edge count of the batch (fill_stats_model) ----
 void count_flops(jamun_sampler* s) {
   const jamun_hparams& hp = s->hp;
+  const ConvModel cm = conv_model(s->plan, hp, s->n_atoms);
   for (auto& L : s->layers) {
     s->flop_ref_per_edge += 2LL * hp.edge_attr_dim * hp.edge_attr_dim + 2LL * (hp.edge_attr_dim + 1) * L.tp_numel;  // SURVEY.md §8 d (SeparableConv: tp_numel = the 336 depth-wise weights)
-    if (s->conv_path == CONV_DG && &L != &s->layers[0]) {
-      // per (tile, k) in k_conv_dg: fp32 path 476 units of v_mfma_f32_32x32x2 (4096 FLOP); f16x3 path 150 v_mfma_f32_32x32x16_f16
-      // (32768 FLOP: 50 groups of 16 inputs x 3 products) + 72 v_mfma_f32_16x16x32_f16 (16384 FLOP); + 60 fp32 units per (32 atoms, k)
-      // in the T pre-pass
-      // (mode 4, jamun_conv_mf.hip: 414 v_mfma_f32_32x32x16_f16 per (tile, k): 228 forming + 186 contraction)
-      const int64_t per_tile_k = s->dg_mode == 5 ? (57LL * ((s->ml_window + 15) / 16) + 186) * 32768 : s->dg_mode == 4 ? (s->mf_nks == 3 ? 357LL : 414LL) * 32768 : s->dg_emu ? (150LL * 32768 + 72LL * 16384) : 476LL * 4096;
-      s->conv_flop_exec_launch = (int64_t)(s->dg_n_tiles - s->n_tail_tiles) * per_tile_k * (hp.edge_attr_dim + 1);  // (tail tiles run in their own kernels)
-      s->flop_exec += s->conv_flop_exec_launch + (int64_t)((s->n_atoms + 31) / 32) * (s->dg_emu ? 24LL * 32768 : 60LL * 4096) * (hp.edge_attr_dim + 1);
-    }
+    if (s->plan.conv_path == CONV_DG && &L != &s->layers[0]) s->flop_exec += cm.conv_flop + cm.tprod_flop;
     else if (L.sep.w2b) s->flop_exec += 3LL * 2 * (int64_t)s->n_atoms * 32 * ((s->S + 31) / 32) * 64 * 352;  // the per-edge weight GEMM as f16x3 (the rest is VALU work per edge)
     else s->flop_exec += 2LL * s->n_pad * (1LL * L.p0.K * L.p0.nt * 32 + 3LL * L.p1.K * L.p1.nt * 32);
   }
 }
 
-// e: edges of the current table; ml_cnt: k_conv_ml's own count of its MFMAs (mode 5 with launches so far; else unused)
+// k_conv_ml counts its own MFMAs (block-sparse forming); the count stands for the model's figure once it has launched
+bool ml_counted(const jamun_sampler* s) { return s->plan.conv_path == CONV_DG && s->plan.dg_mode == DG_ML && s->dev.ml_count && s->ml_launches > 0; }
+
+// e: edges of the current table; ml_cnt: k_conv_ml's own count of its MFMAs (ml_counted; else unused)
 void fill_stats_model(const jamun_sampler* s, int64_t e, unsigned long long ml_cnt, jamun_stats* out) {
   const int64_t m0 = s->hp.mul0, m1 = s->hp.mul1, H1 = s->hp.edge_attr_dim + 1, N = s->n_atoms;
-  const bool dg = s->conv_path == CONV_DG;
+  const bool dg = s->plan.conv_path == CONV_DG, mf = dg && matrix_formed(s->plan.dg_mode);
+  const ConvModel cm = conv_model(s->plan, s->hp, s->n_atoms);
   out->flop_ref_assoc = e * s->flop_ref_per_edge;
   out->flop_executed = s->flop_exec;
   out->conv0_flop_alg = 2 * N * H1 * (m0 + m1) * (m0 + m1);
   out->conv1_flop_alg = 2 * 3 * N * H1 * (m0 + 2 * m1) * m1;
-  out->conv_flop_exec_launch = (s->x1 && s->dg_mode == 4) ? s->conv_flop_exec_launch / 3 : s->conv_flop_exec_launch;
-  if (dg && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0)  // (block-sparse forming: counted by the kernel; mean over its launches so far)
+  out->conv_flop_exec_launch = (s->x1 && s->plan.dg_mode == DG_MF) ? cm.conv_flop / 3 : cm.conv_flop;
+  if (ml_counted(s))  // (block-sparse forming: counted by the kernel; mean over its launches so far)
     out->conv_flop_exec_launch = (int64_t)((double)ml_cnt / (double)s->ml_launches) * 32768;
   if (dg && s->layers.size() > 1)  // one basis for both figures: the hidden layers' share of flop_executed follows the per-launch figure reported above (f16x1: a third; k_conv_ml: kernel-counted)
-    out->flop_executed += (int64_t)(s->layers.size() - 1) * (out->conv_flop_exec_launch - s->conv_flop_exec_launch);
+    out->flop_executed += (int64_t)(s->layers.size() - 1) * (out->conv_flop_exec_launch - cm.conv_flop);
   out->conv_flop_useful_launch = out->conv_bytes_alg_launch = 0;
   if (dg && s->layers.size() > 1) {
     // (the launch these figures describe is the main conv kernel: destinations that go through the tail kernels are not its work — their
     // edges are taken as the batch's mean in-degree, the slab and h~ bytes below stay whole: every slot is read, every slab row written)
-    const int64_t Nm = N - ((s->dg_mode == 4 && s->n_tail_tiles > 0) ? s->n_tail : 0), em = N > 0 ? (int64_t)((double)e * (double)Nm / (double)N) : 0;
+    const int64_t Nm = N - s->plan.n_tail(), em = N > 0 ? (int64_t)((double)e * (double)Nm / (double)N) : 0;
     const int64_t contraction = 2 * H1 * Nm * ((m0 + m1) * (m0 + m1) + 3 * m1 * (2 * m1));
     // per edge and k: x0 (m0), dot 3 m1, x1 3 m1, cross 6 m1, T term 3 m1 — on the matrix cores only in k_conv_mf (k_conv_dg forms on the vector ALUs)
-    const int64_t forming = (s->dg_mode == 4 || s->dg_mode == 5) ? 2 * H1 * em * (m0 + 15 * m1) : 0;
-    out->conv_flop_useful_launch = (s->x1 ? 1 : s->dg_emu ? 3 : 1) * (contraction + forming);
+    const int64_t forming = mf ? 2 * H1 * em * (m0 + 15 * m1) : 0;
+    out->conv_flop_useful_launch = (s->x1 ? 1 : s->plan.dg_emu ? 3 : 1) * (contraction + forming);
     const int64_t slots = (int64_t)s->h_kstride;
     out->conv_bytes_alg_launch = 4 * (H1 * slots          // h~ of the layer
                                       + H1 * 32 * N         // T
                                       + N * s->XS           // feature rows
-                                      + (int64_t)s->dg_n_slabs * s->n_pad * 32 * (s->layers[1].p0.nt + 3 * s->layers[1].p1.nt)) +  // slabs
-                                 ((s->dg_mode == 4 || s->dg_mode == 5) ? H1 * 124 * 64 * 16 : s->dg_emu ? H1 * 4 * 34 * 64 * 16 : H1 * (5 * 16 + 5 * 4 + 2 * 4) * 64 * 16);  // weights
+                                      + (int64_t)s->plan.segs.n_slabs * s->n_pad * 32 * (s->layers[1].p0.nt + 3 * s->layers[1].p1.nt)) +  // slabs
+                                 cm.weight_bytes;
   } else if (s->layers.size() > 1 && s->layers[1].sep.w2b) {
     // SeparableConv hidden layer (k_sep_fused + k_sep_linear): h~ of the layer, one feature row per edge, the per-destination sums written
     // and read once, the slab, W2~ and the Linear's weights once
@@ -424,38 +421,6 @@ void fill_stats_model(const jamun_sampler* s, int64_t e, unsigned long long ml_c
 }
 
 // ---- sampler create, step by step (sampler_create_impl) ---------------------------------------------------------------------------
-struct TopoHost { std::vector<int> graph_of, bip, bis; int nmax = 0; };  // walker of every atom; bonded edges by destination (CSR: pointers, sources); atoms of the largest walker
-
-// validates ptr and the bond list, builds the bonded-edge CSR, sets the edge stride S
-TopoHost check_topology(jamun_sampler* s, const jamun_topology* topo) {
-  const int N = topo->n_atoms, W = topo->n_graphs;
-  TopoHost t;
-  for (int g = 0; g < W; ++g) {
-    if (topo->ptr[g + 1] < topo->ptr[g]) throw Err(JAMUN_ERR_INVALID, "ptr must be non-decreasing");
-    t.nmax = std::max(t.nmax, topo->ptr[g + 1] - topo->ptr[g]);
-  }
-  if (topo->ptr[0] != 0 || topo->ptr[W] != N) throw Err(JAMUN_ERR_INVALID, "ptr must span [0, n_atoms]");
-  t.graph_of.resize(N);
-  for (int g = 0; g < W; ++g)
-    for (int a = topo->ptr[g]; a < topo->ptr[g + 1]; ++a) t.graph_of[a] = g;
-  t.bip.assign(N + 1, 0);
-  t.bis.resize(topo->n_bonds);
-  for (int b = 0; b < topo->n_bonds; ++b) {
-    const int64_t sa = topo->bond_src[b], da = topo->bond_dst[b];
-    if (sa < 0 || sa >= N || da < 0 || da >= N) throw Err(JAMUN_ERR_INVALID, "bond index out of range");
-    if (t.graph_of[sa] != t.graph_of[da]) throw Err(JAMUN_ERR_INVALID, "bond connects two different walkers");
-    t.bip[da + 1]++;
-  }
-  int max_in = 0;
-  for (int i = 0; i < N; ++i) { max_in = std::max(max_in, t.bip[i + 1]); t.bip[i + 1] += t.bip[i]; }
-  std::vector<int> fill(t.bip.begin(), t.bip.end() - 1);
-  for (int b = 0; b < topo->n_bonds; ++b) t.bis[fill[topo->bond_dst[b]]++] = (int)topo->bond_src[b];  // stable: list order
-  s->S = std::min(std::max(t.nmax - 1, 0), JAMUN_MAX_NEIGHBORS + 1) + max_in;
-  if (s->S < 1) s->S = 1;
-  s->n_tiles = s->n_pad / 32;
-  return t;
-}
-
 void set_max_lds() {
   const std::pair<const char*, int (*)()> lds_attr[] = {{"k_conv", conv_set_max_lds}, {"k_node_update", node_update_set_max_lds},
                                                         {"k_conv_init_v", conv_initv_set_max_lds}, {"k_conv_dg", conv_dg_set_max_lds},
@@ -521,9 +486,8 @@ Embeddings upload_embeddings(jamun_sampler* s, const jamun_model* m, const jamun
   return E;
 }
 
-void build_layers(jamun_sampler* s, const jamun_model* m, const Embeddings& E, double c_noise) {
+void build_layers(jamun_sampler* s, const jamun_model* m, const Embeddings& E, double c_noise, bool wide) {
   const jamun_hparams& hp = s->hp;
-  const bool wide = s->conv_path == CONV_WIDE;
   {
     // initial projector: four scalar blocks (irreps not simplified, atom_embedding.py:54-56); scaling already in x_emb
     std::vector<InBlock> ib;
@@ -552,33 +516,37 @@ void build_layers(jamun_sampler* s, const jamun_model* m, const Embeddings& E, d
       if (const char* why = sep_conv_unsupported(L.sep.n0, L.sep.n1, L.p0.nt, L.p1.nt, s->S, hp.edge_attr_dim)) throw Err(JAMUN_ERR_INVALID, why);
 }
 
-// What select_kernels decided, into the sampler: its kernel choice always; for CONV_DG the tile plan, tail tiles and work lists
-void upload_plan(jamun_sampler* s, const KernelPlan& sel) {
+// What packing did, as kernel selection asks it (the one place that looks at the layers' pointers for it)
+PackedLayouts packed_layouts(const std::vector<LayerDev>& layers) {
+  PackedLayouts p;
+  for (size_t l = 1; l < layers.size(); ++l) p.hidden.push_back({layers[l].dg.wx != nullptr, layers[l].dg.wm != nullptr, layers[l].dg.wmt != nullptr});
+  const LayerDev& L0 = layers[0];
+  p.tt2 = L0.tt2 != nullptr; p.tabw = L0.tabw != nullptr; p.wx = L0.wx != nullptr; p.tab_ut = L0.tab_ut; p.nt0 = L0.p0.nt;
+  return p;
+}
+
+// The sampler's plan onto the device: for CONV_DG the tile tables, tail tiles and work lists, and the buffers the plan sizes
+void upload_plan(jamun_sampler* s) {
   DevArena& mem = s->mem;
-  s->conv_path = sel.conv_path;
-  s->init_path = sel.init_path;
-  s->dg_emu = sel.dg_emu;
-  if (sel.conv_path != CONV_DG) {  // the tile plan's weights are not needed: released now, not at destroy
+  const KernelPlan& P = s->plan;
+  PlanDev& d = s->dev;
+  if (P.conv_path != CONV_DG) {  // the tile plan's weights are not needed: released now, not at destroy
     s->dg_mem.clear();
     for (auto& L : s->layers) L.dg = DgDev{};
     return;
   }
   const int N = s->n_atoms, n_k = s->hp.edge_attr_dim + 1;
-  const TilePlan& T = sel.tiles;
-  s->dg_mode = sel.dg_mode; s->dg_row_blocks = T.row_blocks; s->dg_RS = sel.dg_RS; s->dg_n_tiles = (int)T.atoms.size();
-  s->ml_window = sel.ml_window; s->mf_nks = sel.mf_nks; s->initv_nbuf = sel.initv_nbuf; s->init_tail = sel.init_tail;
-  s->dg_grid = s->cus; s->dg_ng = sel.ng; s->dg_seg_cost_tenths = (int)std::lround(10 * sel.seg_cost);
-  if (!sel.tail_tiles.empty()) {
-    s->n_tail_tiles = (int)sel.tail_tiles.size(); s->n_tail = (int)sel.tail_atom.size(); s->tail_runs = sel.tail_runs;
-    s->tail_tiles = mem.upload(sel.tail_tiles);
-    s->tail_atom = mem.upload(sel.tail_atom);
-    s->tail_scale = mem.alloc<float>(sel.tail_atom.size());
-    s->tail_P = mem.alloc<float4>(sel.tail_P_bytes / 16);
+  const TilePlan& T = P.tiles;
+  if (P.n_tail_tiles()) {
+    d.tail_tiles = mem.upload(P.tail_tiles);
+    d.tail_atom = mem.upload(P.tail_atom);
+    d.tail_scale = mem.alloc<float>(P.tail_atom.size());
+    d.tail_P = mem.alloc<float4>(P.tail_P_bytes / 16);
   }
-  // (round 6) every segment record carries its tile's descriptor — {k_extra, first destination, destinations | source rows << 8, first source row} —
+  // every segment record carries its tile's descriptor — {k_extra, first destination, destinations | source rows << 8, first source row} —
   // so that a kernel's first prologue is ONE round trip behind the segment list instead of two (list -> tile tables -> loads)
-  auto upload = [&](const SegPlan& P, int4*& segs_dev, int*& atom_nslab, int& max_segs, int& n_slabs) {
-    std::vector<int4> segs = P.segs;
+  auto upload = [&](const SegPlan& L, int4*& segs_dev, int*& atom_nslab) {
+    std::vector<int4> segs = L.segs;
     for (size_t i = 0; i + 1 < segs.size(); i += 2) {
       const int t = segs[i].x;
       if (t < 0) continue;
@@ -586,30 +554,29 @@ void upload_plan(jamun_sampler* s, const KernelPlan& sel) {
       segs[i + 1].z = T.atoms[t].y | ((T.span[t].y - T.span[t].x) << 8);
       segs[i + 1].w = T.span[t].x;
     }
-    segs_dev = mem.upload(segs); atom_nslab = mem.upload(P.atom_nslab); max_segs = P.max_segs; n_slabs = P.n_slabs;
+    segs_dev = mem.upload(segs); atom_nslab = mem.upload(L.atom_nslab);
   };
-  if (sel.own_init_segs) upload(sel.init_segs, s->init_segs, s->init_atom_nslab, s->init_max_segs, s->init_n_slabs);
-  upload(sel.segs, s->dg_segs, s->dg_atom_nslab, s->dg_max_segs, s->dg_n_slabs);
-  s->dg_tile_atoms = mem.upload(T.atoms);
-  s->dg_tile_span = mem.upload(T.span);
-  const bool mf = s->dg_mode == 4 || s->dg_mode == 5;
-  if (s->dg_mode == 5) s->ml_count = mem.zeroed<unsigned long long>(1);
-  if (mf) {
-    s->dg_tstride = ((N + 31) & ~31) + 64;
-    s->dg_T = mem.zeroed<float>((size_t)n_k * 32 * s->dg_tstride);
-    s->mf_err = mem.zeroed<int>(1);
-    s->mf_err_host = mem.pinned<int>(1);
-    *s->mf_err_host = 0;
+  if (P.own_init_segs) upload(P.init_segs, d.init_segs, d.init_atom_nslab);
+  upload(P.segs, d.segs, d.atom_nslab);
+  d.tile_atoms = mem.upload(T.atoms);
+  d.tile_span = mem.upload(T.span);
+  if (P.dg_mode == DG_ML) d.ml_count = mem.zeroed<unsigned long long>(1);
+  if (matrix_formed(P.dg_mode)) {
+    d.tstride = ((N + 31) & ~31) + 64;
+    d.T = mem.zeroed<float>((size_t)n_k * 32 * d.tstride);
+    d.mf_err = mem.zeroed<int>(1);
+    d.mf_err_host = mem.pinned<int>(1);
+    *d.mf_err_host = 0;
   } else {
-    s->dg_T = mem.alloc<float>((size_t)n_k * N * 32);
+    d.T = mem.alloc<float>((size_t)n_k * N * 32);
   }
-  s->x1 = (s->tune.f16x1 && mf && s->dg_emu) ? 1 : 0;
+  s->x1 = (s->tune.f16x1 && matrix_formed(P.dg_mode) && P.dg_emu) ? 1 : 0;
 }
 
 void alloc_work_buffers(jamun_sampler* s) {
   DevArena& mem = s->mem;
   const jamun_hparams& hp = s->hp;
-  const bool wide = s->conv_path == CONV_WIDE;
+  const bool wide = s->plan.conv_path == CONV_WIDE;
   const size_t N = (size_t)s->n_atoms, NS = N * s->S;
   for (float** p : {&s->yc, &s->g, &s->tmp, &s->xhat_buf, &s->score_buf, &s->psi}) *p = mem.alloc<float>(N * 3);
   s->deg = mem.alloc<int>(N);
@@ -632,7 +599,7 @@ void alloc_work_buffers(jamun_sampler* s) {
   s->h = mem.alloc<float>(s->h_stride * (s->h_batched ? s->layers.size() : 1) + 32 * (size_t)s->S + 256);
   int nt0 = 0, nt1 = 0;
   for (auto& L : s->layers) { nt0 = std::max(nt0, L.p0.nt); nt1 = std::max(nt1, L.p1.nt); }
-  const size_t n_part = (size_t)std::max(std::max(s->n_slices, s->dg_n_slabs), s->init_n_slabs);
+  const size_t n_part = (size_t)std::max(std::max(s->n_slices, s->plan.segs.n_slabs), s->plan.init_segs.n_slabs);  // (1 each without a tile plan)
   s->partial0 = mem.alloc<float>(n_part * s->n_pad * nt0 * 32);
   s->partial1 = mem.alloc<float>(n_part * s->n_pad * 3 * nt1 * 32);
   {
@@ -651,13 +618,18 @@ void alloc_work_buffers(jamun_sampler* s) {
   s->counter = mem.alloc<unsigned long long>(1);
 }
 
-std::unique_ptr<jamun_sampler> sampler_create_impl(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning) {
+jamun_tuning checked_tuning(const jamun_tuning* tuning) {
   jamun_tuning tn{};
   if (tuning) tn = *tuning;
   if (tn.dg_kgroups != 0 && tn.dg_kgroups != 1 && tn.dg_kgroups != 2 && tn.dg_kgroups != 4 && tn.dg_kgroups != 8)
     throw Err(JAMUN_ERR_INVALID, "jamun_tuning.dg_kgroups must be 0 (default), 1, 2, 4 or 8");
   if (tn.f16x1 != 0 && tn.f16x1 != 1) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.f16x1 must be 0 or 1");
   if (tn.seg_cost_tenths < -1 || tn.seg_cost_tenths > 1000) throw Err(JAMUN_ERR_INVALID, "jamun_tuning.seg_cost_tenths must be -1 (no segment cost), 0 (default) or 1..1000");
+  return tn;
+}
+
+std::unique_ptr<jamun_sampler> sampler_create_impl(const jamun_model* m, float sigma, const jamun_topology* topo, const jamun_tuning* tuning) {
+  const jamun_tuning tn = checked_tuning(tuning);
   if (!(sigma > 0)) throw Err(JAMUN_ERR_INVALID, "sigma must be positive");
   if (topo->n_atoms < 1 || topo->n_graphs < 1) throw Err(JAMUN_ERR_INVALID, "empty walker batch");
   const jamun_hparams& hp = m->hp;
@@ -667,7 +639,7 @@ std::unique_ptr<jamun_sampler> sampler_create_impl(const jamun_model* m, float s
   s->n_pad = ((topo->n_atoms + 31) / 32) * 32;
   s->XS = hp.mul0 + 3 * hp.mul1;
   s->n_emb = hp.emb_dim[0] + hp.emb_dim[1] + hp.emb_dim[2] + hp.emb_dim[3];
-  s->conv_path = base_conv_path(hp, s->n_emb);
+  const ConvPath base = base_conv_path(hp, s->n_emb);
   // ---- normalisation factors in fp32, op for op as Denoiser.normalization_factors (denoiser.py:116-136,177-178)
   {
     const float A = hp.average_squared_distance;
@@ -680,21 +652,23 @@ std::unique_ptr<jamun_sampler> sampler_create_impl(const jamun_model* m, float s
     s->r2 = s->r_cut * s->r_cut;
   }
   const double c_noise = std::log((double)sigma) / 4.0;
-  const TopoHost th = check_topology(s.get(), topo);
+  const TopoHost th = check_topology(*topo);
+  s->S = th.S;
   set_max_lds();
   s->ptr = s->mem.upload(std::vector<int>(topo->ptr, topo->ptr + topo->n_graphs + 1));
   s->bond_in_ptr = s->mem.upload(th.bip);
   s->bond_in_src = s->mem.upload(th.bis);
   upload_radial_centres(s.get());
   const Embeddings E = upload_embeddings(s.get(), m, topo, c_noise);
-  build_layers(s.get(), m, E, c_noise);
+  build_layers(s.get(), m, E, c_noise, base == CONV_WIDE);
   pack_head(*m, s.get());
   int dev = 0, cus = 0;
   HIPCHECK(hipGetDevice(&dev));
   HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   s->cus = std::max(cus, 1);
   // ---- kernel selection (jamun_plan.cpp); upload of the tile plan and work lists of the destination-grouped kernels
-  upload_plan(s.get(), select_kernels(hp, tn, *topo, th.graph_of, th.nmax, s->S, s->cus, s->conv_path, s->layers, s->n_uniq, s->atom_uid != nullptr));
+  s->plan = select_kernels(hp, tn, *topo, th, s->cus, base, packed_layouts(s->layers), s->n_uniq, s->atom_uid != nullptr);
+  upload_plan(s.get());
   alloc_work_buffers(s.get());
   count_flops(s.get());
   HIPCHECK(hipDeviceSynchronize());
@@ -754,7 +728,7 @@ int jamun_sampler_create(const jamun_model* m, float sigma, const jamun_topology
 // implementation and is not checked; neither is the wide path (jamun_wide.hip): it IS the general path for the models it serves (fp32
 // MFMAs / vector ALUs, no host-planned tiles), so it selects no specialised kernel and builds no second sampler.  Cost: one general-kernel forward + the packing of its weights (cfg2: 0.3 s, once per sampler).
 static void sampler_self_check(const jamun_model* m, float sigma, const jamun_topology* topo, jamun_sampler* s) {
-  if (s->conv_path != CONV_DG) return;  // (the specialised kernels, the initial projector's included, all run on the destination-grouped tile plan)
+  if (s->plan.conv_path != CONV_DG) return;  // (the specialised kernels, the initial projector's included, all run on the destination-grouped tile plan)
   jamun_tuning rt{};
   rt.no_dg = rt.no_mf = rt.no_mfi = rt.no_init_v = rt.no_ml = rt.no_tail = 1;
   rt.node_fp32 = rt.edge_h_fp32 = 1;
@@ -806,13 +780,13 @@ static void sampler_self_check(const jamun_model* m, float sigma, const jamun_to
     if (!finite || dv > tol * std::max(mx, 1e-6)) {
       char msg[320];
       snprintf(msg, sizeof msg, "create-time self-check failed: %s%d of the selected kernels (conv path %d, mode %d, initial projector %d) deviates from the general kernels by %.3g of its largest value (bound %.0e)%s — this build must not sample",
-               what, layer, (int)s->conv_path, s->dg_mode, (int)s->init_path, finite ? dv / std::max(mx, 1e-6) : NAN, tol, finite ? "" : " (non-finite values)");
+               what, layer, (int)s->plan.conv_path, (int)s->plan.dg_mode, (int)s->plan.init_path, finite ? dv / std::max(mx, 1e-6) : NAN, tol, finite ? "" : " (non-finite values)");
       throw Err(JAMUN_ERR_INVALID, msg);
     }
   };
   for (size_t l = 0; l < s->layers.size(); ++l) compare(s->x[l], r->x[l], (size_t)n_cmp * s->XS, "node features after block ", (int)l);
   compare(s->g, r->g, (size_t)n_cmp * 3, "network output g, block ", (int)s->layers.size());
-  if (s->ml_count) { HIPCHECK(hipMemset(s->ml_count, 0, sizeof(unsigned long long))); s->ml_launches = 0; }  // (the check's launches are not the run's)
+  if (s->dev.ml_count) { HIPCHECK(hipMemset(s->dev.ml_count, 0, sizeof(unsigned long long))); s->ml_launches = 0; }  // (the check's launches are not the run's)
   s->edges_built = false;
 }
 void jamun_sampler_destroy(jamun_sampler* s) { delete s; }
@@ -1067,32 +1041,32 @@ int jamun_sampler_stats(jamun_sampler* s, jamun_stats* out, void* stream) {
     unsigned long long e = 0;
     HIPCHECK(hipMemcpyAsync(&e, s->counter, sizeof(e), hipMemcpyDeviceToHost, st));
     int mf_flag = 0;
-    if (s->mf_err) HIPCHECK(hipMemcpyAsync(&mf_flag, s->mf_err, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (s->dev.mf_err) HIPCHECK(hipMemcpyAsync(&mf_flag, s->dev.mf_err, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     // (k_conv_mf / k_conv_mfi: an ordered pair with more than three edges cannot share one coefficient entry; the host excludes such
     // topologies at create time, the kernels still flag what they see)
     if (mf_flag != 0) {
-      if (s->mf_err_host) *s->mf_err_host = mf_flag;
+      if (s->dev.mf_err_host) *s->dev.mf_err_host = mf_flag;
       mf_err_check(s);
     }
-    const bool dg = s->conv_path == CONV_DG;
+    const bool dg = s->plan.conv_path == CONV_DG;
     unsigned long long ml_cnt = 0;
-    if (dg && s->dg_mode == 5 && s->ml_count && s->ml_launches > 0) HIPCHECK(hipMemcpy(&ml_cnt, s->ml_count, sizeof(ml_cnt), hipMemcpyDeviceToHost));
+    if (ml_counted(s)) HIPCHECK(hipMemcpy(&ml_cnt, s->dev.ml_count, sizeof(ml_cnt), hipMemcpyDeviceToHost));
     fill_stats_model(s, (int64_t)e, ml_cnt, out);
     out->n_edges = (int64_t)e;
     out->conv_k0 = s->layers.back().p0.K;
     out->conv_k1 = s->layers.back().p1.K;
     out->edge_stride = s->S;
-    out->n_slices = dg ? s->dg_n_slabs : s->n_slices;
-    out->conv_path = std::max(0, (int)s->conv_path);  // (SeparableConv: reported as 0, like the general kernels)
-    out->dg_mode = dg ? s->dg_mode : -1;
-    out->init_path = std::max(0, (int)s->init_path);
-    out->dg_row_blocks = dg && s->dg_row_blocks ? 1 : 0;
-    out->dg_emu = s->conv_path == CONV_WIDE ? 0 : dg ? (s->x1 ? 2 : s->dg_emu) : -1;  // (the wide path: fp32 MFMAs, jamun_tuning.f16x1 ignored)
-    out->n_tail_tiles = s->n_tail_tiles;
-    out->n_tail = s->n_tail;
-    out->mf_nks = (dg && s->dg_mode == 4) ? s->mf_nks : 0;
-    out->ml_window = (dg && s->dg_mode == 5) ? s->ml_window : 0;
+    out->n_slices = dg ? s->plan.segs.n_slabs : s->n_slices;
+    out->conv_path = std::max(0, (int)s->plan.conv_path);  // (SeparableConv: reported as 0, like the general kernels)
+    out->dg_mode = dg ? (int)s->plan.dg_mode : -1;
+    out->init_path = std::max(0, (int)s->plan.init_path);
+    out->dg_row_blocks = dg && s->plan.tiles.row_blocks ? 1 : 0;
+    out->dg_emu = s->plan.conv_path == CONV_WIDE ? 0 : dg ? (s->x1 ? 2 : s->plan.dg_emu) : -1;  // (the wide path: fp32 MFMAs, jamun_tuning.f16x1 ignored)
+    out->n_tail_tiles = s->plan.n_tail_tiles();
+    out->n_tail = s->plan.n_tail();
+    out->mf_nks = (dg && s->plan.dg_mode == DG_MF) ? s->plan.mf_nks : 0;
+    out->ml_window = dg ? s->plan.ml_window : 0;  // (set with DG_ML only)
   });
 }
 
@@ -1213,33 +1187,72 @@ int jamun_debug_plan_segments(int32_t cus, int32_t ng, int32_t n_k, int32_t n_at
   });
 }
 
+int jamun_debug_select_kernels(const jamun_hparams* hp, const jamun_tuning* tuning, const jamun_topology* topo, int32_t cus, int32_t n_uniq,
+                               int32_t have_atom_uid, int32_t n_hidden, const int32_t* hidden, const int32_t* layer0, int64_t* out24,
+                               int32_t which, int32_t* list, int64_t capacity, int64_t* list_len) {
+  return guarded([&] {
+    if (!hp || !topo || !layer0 || !out24 || !list_len || (n_hidden > 0 && !hidden)) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (cus < 1 || n_hidden < 0 || topo->n_atoms < 1 || topo->n_graphs < 1) throw Err(JAMUN_ERR_INVALID, "bad sizes");
+    const jamun_tuning tn = checked_tuning(tuning);
+    PackedLayouts lay;
+    for (int l = 0; l < n_hidden; ++l) lay.hidden.push_back({(hidden[l] & 1) != 0, (hidden[l] & 2) != 0, (hidden[l] & 4) != 0});
+    lay.tt2 = layer0[0] != 0; lay.tabw = layer0[1] != 0; lay.tab_ut = layer0[2]; lay.wx = layer0[3] != 0; lay.nt0 = layer0[4];
+    // (the sampler's own selection: the same functions, only the layout flags come from the caller)
+    const TopoHost th = check_topology(*topo);
+    const ConvPath base = base_conv_path(*hp, hp->emb_dim[0] + hp->emb_dim[1] + hp->emb_dim[2] + hp->emb_dim[3]);
+    const KernelPlan P = select_kernels(*hp, tn, *topo, th, cus, base, lay, n_uniq, have_atom_uid != 0);
+    const TilePlan& T = P.tiles;
+    const int64_t v[24] = {P.conv_path, P.dg_mode, P.init_path, P.dg_emu, P.dg_RS, th.S, (int64_t)T.atoms.size(), T.span_max, T.row_blocks,
+                           (int64_t)P.tail_tiles.size(), (int64_t)P.tail_atom.size(), P.tail_runs, P.init_tail, P.own_init_segs, P.mf_nks, P.ml_window,
+                           P.initv_nbuf, P.ng, std::lround(10 * P.seg_cost), P.segs.max_segs, P.segs.n_slabs, conv_model(P, *hp, topo->n_atoms).conv_flop,
+                           P.init_segs.max_segs, P.init_segs.n_slabs};
+    std::copy(v, v + 24, out24);
+    std::vector<int32_t> flat;
+    auto int4s = [&](const std::vector<int4>& r) { for (const int4& q : r) flat.insert(flat.end(), {q.x, q.y, q.z, q.w}); };
+    switch (which) {
+      case -1: break;
+      case 0: int4s(P.segs.segs); break;
+      case 1: if (P.own_init_segs) int4s(P.init_segs.segs); break;
+      case 2: int4s(P.tail_tiles); break;
+      case 3: for (size_t t = 0; t < T.atoms.size(); ++t) flat.insert(flat.end(), {T.atoms[t].x, T.atoms[t].y, T.span[t].x, T.span[t].y}); break;
+      case 4: flat = P.segs.atom_nslab; break;
+      case 5: if (P.own_init_segs) flat = P.init_segs.atom_nslab; break;
+      case 6: flat = T.chunk; break;
+      default: throw Err(JAMUN_ERR_INVALID, "unknown work list");
+    }
+    *list_len = (int64_t)flat.size();
+    if (!list || flat.empty()) return;
+    if ((int64_t)flat.size() > capacity) throw Err(JAMUN_ERR_INVALID, "list too small: needs list_len values");
+    std::copy(flat.begin(), flat.end(), list);
+  });
+}
+
 int jamun_debug_segments(jamun_sampler* s, int32_t which, int32_t* out, int64_t capacity, int32_t* info) {
   return guarded([&] {
     if (!s || !info) throw Err(JAMUN_ERR_INVALID, "null argument");
-    if (s->conv_path != CONV_DG) throw Err(JAMUN_ERR_INVALID, "the sampler has no destination-grouped plan (jamun_tuning.no_dg)");
+    if (s->plan.conv_path != CONV_DG) throw Err(JAMUN_ERR_INVALID, "the sampler has no destination-grouped plan (jamun_tuning.no_dg)");
     const void* src = nullptr;
     int64_t n = 0;
-    int max_segs = s->dg_max_segs, n_slabs = s->dg_n_slabs;
+    const KernelPlan& P = s->plan;
+    const SegPlan& L = which == 1 ? P.init_segs : P.segs;
+    const bool have = which != 1 || P.own_init_segs;  // (without lists of its own the initial projector runs list 0: nothing to report)
     switch (which) {
-      case 0: src = s->dg_segs; n = (int64_t)s->dg_grid * s->dg_max_segs * 8; break;
-      case 1:
-        max_segs = s->init_max_segs; n_slabs = s->init_n_slabs;
-        if (s->init_segs) { src = s->init_segs; n = (int64_t)s->dg_grid * s->init_max_segs * 8; }
-        break;
-      case 2: src = s->tail_tiles; n = (int64_t)s->n_tail_tiles * 4; break;
-      case 3: n = (int64_t)s->dg_n_tiles * 4; break;
-      case 4: src = s->dg_atom_nslab; n = s->n_atoms; break;
-      case 5: if (s->init_atom_nslab) { src = s->init_atom_nslab; n = s->n_atoms; } break;
+      case 0: src = s->dev.segs; n = (int64_t)L.segs.size() * 4; break;
+      case 1: if (have) { src = s->dev.init_segs; n = (int64_t)L.segs.size() * 4; } break;
+      case 2: src = s->dev.tail_tiles; n = (int64_t)P.n_tail_tiles() * 4; break;
+      case 3: n = (int64_t)P.n_tiles() * 4; break;
+      case 4: src = s->dev.atom_nslab; n = s->n_atoms; break;
+      case 5: if (P.own_init_segs) { src = s->dev.init_atom_nslab; n = s->n_atoms; } break;
       default: throw Err(JAMUN_ERR_INVALID, "unknown work list");
     }
-    const int32_t v[9] = {(int32_t)n, s->dg_grid, max_segs, n_slabs, s->dg_ng, s->hp.edge_attr_dim + 1, s->dg_n_tiles, s->dg_seg_cost_tenths, s->tail_runs};
+    const int32_t v[9] = {(int32_t)n, s->cus, have ? L.max_segs : 0, have ? L.n_slabs : 0, P.ng, s->hp.edge_attr_dim + 1, P.n_tiles(), (int32_t)std::lround(10 * P.seg_cost), P.tail_runs};
     std::copy(v, v + 9, info);
     if (!out || n == 0) return;
     if (n > capacity) throw Err(JAMUN_ERR_INVALID, "out too small: needs info[0] values");
     if (which == 3) {  // {first atom, atoms, first source row, end of the source rows} per tile
-      std::vector<int2> a((size_t)s->dg_n_tiles), sp((size_t)s->dg_n_tiles);
-      HIPCHECK(hipMemcpy(a.data(), s->dg_tile_atoms, a.size() * sizeof(int2), hipMemcpyDeviceToHost));
-      HIPCHECK(hipMemcpy(sp.data(), s->dg_tile_span, sp.size() * sizeof(int2), hipMemcpyDeviceToHost));
+      std::vector<int2> a((size_t)P.n_tiles()), sp((size_t)P.n_tiles());
+      HIPCHECK(hipMemcpy(a.data(), s->dev.tile_atoms, a.size() * sizeof(int2), hipMemcpyDeviceToHost));
+      HIPCHECK(hipMemcpy(sp.data(), s->dev.tile_span, sp.size() * sizeof(int2), hipMemcpyDeviceToHost));
       for (size_t t = 0; t < a.size(); ++t) {
         out[4 * t] = a[t].x; out[4 * t + 1] = a[t].y; out[4 * t + 2] = sp[t].x; out[4 * t + 3] = sp[t].y;
       }

@@ -162,19 +162,88 @@ LayerDev build_layer(DevArena& mem, DevArena& dg_mem, const jamun_model& m, cons
 // conv_path / init_path (include/jamun_hip.h); SeparableConv has enumerators of its own here and is reported as 0 (jamun_sampler_stats).
 enum ConvPath {
   CONV_GENERAL = 0,  // k_conv (jamun_conv.hip)
-  CONV_DG = 2,       // destination-grouped, on host-planned tiles: k_conv_dg / k_conv_mf / k_conv_ml by jamun_sampler::dg_mode
+  CONV_DG = 2,       // destination-grouped, on host-planned tiles: k_conv_dg / k_conv_mf / k_conv_ml by KernelPlan::dg_mode
   CONV_WIDE = 3,     // k_conv_wide (jamun_wide.hip): a Conv model outside the envelope of the compiled-width kernels
   CONV_SEP = -1      // SeparableConv (jamun_sepconv.hip)
 };
 enum InitPath {
   INIT_GENERAL = 0,
   INIT_V = 2,    // k_conv_init_v (tiles / segments of the dg kernel)
-  INIT_MFI = 3,  // k_conv_mfi (mode 4 tiles, at most 32 distinct embedding rows)
-  INIT_MFX = 4,  // k_conv_mfx (mode 4 tiles, any number of distinct rows: formed from the feature rows)
-  INIT_MLX = 5,  // k_conv_mlx (mode 5 tiles: large spans)
+  INIT_MFI = 3,  // k_conv_mfi (DG_MF tiles, at most 32 distinct embedding rows)
+  INIT_MFX = 4,  // k_conv_mfx (DG_MF tiles, any number of distinct rows: formed from the feature rows)
+  INIT_MLX = 5,  // k_conv_mlx (DG_ML tiles: large spans)
   INIT_WIDE = 6,
   INIT_SEP = -1
 };
+// The hidden-layer kernel of CONV_DG.  jamun_stats.dg_mode publishes these numbers; DgArgs::alt receives those of the k_conv_dg variants.
+enum DgMode {
+  DG_RESIDENT = 0,  // k_conv_dg: two phases per hidden unit, source rows resident in LDS (spans up to ~80 rows)
+  DG_ALT = 1,       // k_conv_dg: alternating residency (molecules above that, up to ~176 atoms)
+  DG_SINGLE = 2,    // k_conv_dg: single phase with double-buffered A tiles (spans up to ~52 rows)
+  DG_SINGLE_Y = 3,  // k_conv_dg: single phase with a double-buffered X tile and one Y tile (spans up to ~73 rows)
+  DG_MF = 4,        // k_conv_mf (+ tail tiles): A operand formed on the matrix cores, spans within one K = 64 window (62 rows)
+  DG_ML = 5         // k_conv_ml: its two-pass, block-sparse variant for spans of 63..167 rows
+};
+inline bool matrix_formed(DgMode m) { return m == DG_MF || m == DG_ML; }
+// which plans at hand the trial of k_conv_mf / of k_conv_ml may replace (select_kernels)
+inline bool mf_may_replace(DgMode m) { return m == DG_RESIDENT || m == DG_SINGLE || m == DG_SINGLE_Y; }
+inline bool ml_may_replace(DgMode m) { return m == DG_RESIDENT || m == DG_ALT || m == DG_SINGLE_Y; }
+
+// ---- what jamun_plan.cpp decides ---------------------------------------------------------------------
+struct SegPlan {
+  std::vector<int4> segs;  // [cus][max_segs][2]
+  int max_segs = 1, n_slabs = 1;
+  std::vector<int> atom_nslab;
+};
+struct TilePlan {
+  std::vector<int2> atoms, span;  // per tile: {first destination atom, atoms}, {lo, hi} source atoms
+  std::vector<int> chunk;         // ... and its destination chunk (tiles of one chunk number their partial slabs jointly)
+  int n_chunks = 0, span_max = 0;
+  bool row_blocks = false;        // a molecule's sources were cut into row blocks
+};
+// What select_kernels decides: which kernels run — jamun_stats reports the numbers — and, for CONV_DG, the tiles and work lists they run
+// on.  A sampler keeps the plan it was created with, unmodified; dispatch, the stats and jamun_debug_segments read it.  Below init_path the
+// fields are meaningful for CONV_DG only.
+struct KernelPlan {
+  ConvPath conv_path = CONV_GENERAL;
+  InitPath init_path = INIT_GENERAL;
+  DgMode dg_mode = DG_RESIDENT;
+  int dg_emu = 1;  // 1: f16x3 contraction (three f16 MFMAs per fp32 product); 0 (jamun_tuning.dg_fp32): v_mfma_f32_32x32x2_f32
+  int dg_RS = 0;   // source rows of a tile in LDS
+  TilePlan tiles;
+  int ng = 1;             // k-slices over XCD groups and ...
+  double seg_cost = 0.0;  // ... the cost of a segment, in items, the work lists were cut with
+  SegPlan segs, init_segs;     // work lists of the hidden layers; of the initial projector when it keeps lists of its own (own_init_segs)
+  bool own_init_segs = false, init_tail = false;
+  std::vector<int4> tail_tiles;  // tail tiles (DG_MF): records, destinations, runs of hidden units, bytes of the parked operands
+  std::vector<int> tail_atom;
+  int tail_runs = 0;
+  size_t tail_P_bytes = 0;
+  int mf_nks = 4;      // forming K-steps of k_conv_mf (3: every whole tile's sources lie in the first 48 rows of its window)
+  int ml_window = 0;   // DG_ML: source rows of the instantiation (96, 128, 168)
+  int initv_nbuf = 2;  // INIT_V: row buffers of k_conv_init_v in LDS
+  int n_tiles() const { return (int)tiles.atoms.size(); }
+  int n_tail_tiles() const { return (int)tail_tiles.size(); }
+  int n_tail() const { return (int)tail_atom.size(); }
+};
+// The device arrays uploaded from a CONV_DG plan (upload_plan), and the buffers sized by it
+struct PlanDev {
+  int2 *tile_atoms = nullptr, *tile_span = nullptr;
+  int4 *segs = nullptr, *init_segs = nullptr;  // segment records with their tile's descriptor (init_segs: KernelPlan::own_init_segs)
+  int *atom_nslab = nullptr, *init_atom_nslab = nullptr;
+  // tail tiles (tiles with few destinations): formed with the hidden unit in the column index and contracted 32 gathered destinations at a
+  // time (k_tail_form / k_tail_contract) instead of as whole tiles of k_conv_mf
+  int4* tail_tiles = nullptr;
+  int* tail_atom = nullptr;
+  float* tail_scale = nullptr;
+  float4* tail_P = nullptr;
+  float* T = nullptr;  // [n_k][n_atoms][32] pre-pass product of a hidden layer (k_tprod), reused by every layer
+  int tstride = 0;     // matrix-formed kernels: T is [n_k][32][tstride], transposed
+  unsigned long long* ml_count = nullptr;  // v_mfma_f32_32x32x16_f16 executed by k_conv_ml since create (depends on the occupied source blocks)
+  int* mf_err = nullptr;       // device flag of the matrix-formed kernels
+  int* mf_err_host = nullptr;  // pinned copy, refreshed behind every entry point that ran a forward (mf_err_fetch / mf_err_check)
+};
+
 
 struct jamun_sampler {
   DevArena mem, dg_mem;  // every device buffer below (dg_mem: LayerDev::dg); declared first: freed last, after the event pool
@@ -187,43 +256,14 @@ struct jamun_sampler {
   // static device data
   int *ptr = nullptr, *bond_in_ptr = nullptr, *bond_in_src = nullptr;
   int n_tiles = 0;
-  // which kernels run (select_kernels): the hidden layers' conv and the initial projector's; jamun_stats reports these numbers
-  ConvPath conv_path = CONV_GENERAL;
-  InitPath init_path = INIT_GENERAL;
-  int initv_nbuf = 2;                 // INIT_V: row buffers of k_conv_init_v in LDS
-  int* atom_uid = nullptr;            // [n_atoms] index of the atom's distinct (scaled) embedding row
-  // destination-grouped VALU-forming conv kernel (jamun_conv_dg.hip; hidden layers): own tile plan (larger source spans)
-  bool dg_row_blocks = false;
-  int dg_mode = 0;  // 0 two-phase resident, 1 alternating residency, 2 single phase (see jamun_sampler_create)
-  int dg_emu = 1;   // 1: f16x3 contraction (three f16 MFMAs per fp32 product); 0 (jamun_tuning.dg_fp32): v_mfma_f32_32x32x2_f32; stats report 2 for the opt-in f16x1 mode (s->x1)
-  int dg_RS = 0, dg_grid = 0, dg_max_segs = 0, dg_n_slabs = 0, dg_n_tiles = 0;
-  int dg_ng = 1, dg_seg_cost_tenths = 0;  // k-slices and segment cost the work lists were cut with (jamun_debug_segments)
-  int2 *dg_tile_atoms = nullptr, *dg_tile_span = nullptr;
-  int4* dg_segs = nullptr;
-  int* dg_atom_nslab = nullptr;
-  float* sep_D = nullptr;  // SeparableConv: [n_atoms][K0 + 3 K1] per-destination sums of the layer at hand
+  KernelPlan plan;  // which kernels run and on which tiles and work lists (select_kernels); not modified after create
+  PlanDev dev;      // ... and what upload_plan put on the device for them
+  int* atom_uid = nullptr;  // [n_atoms] index of the atom's distinct (scaled) embedding row
+  float* sep_D = nullptr;   // SeparableConv: [n_atoms][K0 + 3 K1] per-destination sums of the layer at hand
   int cus = 1;
-  float* dg_T = nullptr;  // [n_k][n_atoms][32] pre-pass product of a hidden layer (k_tprod), reused by every layer
-  int dg_tstride = 0;     // mode 4 (jamun_conv_mf.hip): dg_T is [n_k][32][dg_tstride], transposed
-  // tail tiles of the mode-4 plan (tiles with few destinations): formed with the hidden unit in the column index and contracted 32 gathered
-  // destinations at a time (k_tail_form / k_tail_contract) instead of as whole tiles of k_conv_mf; the initial projector keeps them as tiles
-  int n_tail_tiles = 0, n_tail = 0, tail_runs = 0;
-  int mf_nks = 4;  // forming K-steps of k_conv_mf (3: every whole tile's sources lie in the first 48 rows of its window)
-  int x1 = 0;         // 1: reduced-precision hidden-layer conv (jamun_tuning.f16x1) — honoured by k_conv_mf / k_conv_ml (dg_mode 4 / 5) only
-  int ml_window = 0;  // mode 5 (jamun_conv_ml.hip): source rows of the instantiation (96, 128, 168)
-  unsigned long long* ml_count = nullptr;  // device: v_mfma_f32_32x32x16_f16 executed by k_conv_ml since create (depends on the occupied source blocks)
-  int64_t ml_launches = 0;                 // ... over this many launches
-  int4* tail_tiles = nullptr;
-  int* tail_atom = nullptr;
-  float* tail_scale = nullptr;
-  float4* tail_P = nullptr;
-  int4* init_segs = nullptr;   // segment lists of the initial projector (ALL tiles) when the hidden layers' lists leave the tail tiles out
-  int* init_atom_nslab = nullptr;
-  int init_max_segs = 0, init_n_slabs = 0;
-  bool init_tail = false;      // the initial projector sends the tail tiles through k_tail_form_init / k_tail_contract as well
-  int n_uniq = 0;         // distinct (noise-scaled) embedding rows of the batch
-  int* mf_err = nullptr;  // device flag of k_conv_mf
-  int* mf_err_host = nullptr;  // pinned copy, refreshed behind every entry point that ran a forward (mf_err_fetch / mf_err_check)
+  int x1 = 0;  // 1: reduced-precision hidden-layer conv (jamun_tuning.f16x1) — honoured by the matrix-formed kernels only; stats report dg_emu 2
+  int64_t ml_launches = 0;  // launches of k_conv_ml behind PlanDev::ml_count
+  int n_uniq = 0;  // distinct (noise-scaled) embedding rows of the batch
   float *x_emb = nullptr, *mu = nullptr;
   float *z0 = nullptr, *z1 = nullptr;  // CONV_WIDE: node-update operands (NodeWideArgs::z0 / z1)
   std::vector<LayerDev> layers;
@@ -241,7 +281,7 @@ struct jamun_sampler {
   float4* egeo = nullptr;
   std::vector<float*> x;  // per block output [n_atoms][XS]
   unsigned long long* counter = nullptr;
-  int64_t flop_ref_per_edge = 0, flop_exec = 0, conv_flop_exec_launch = 0;
+  int64_t flop_ref_per_edge = 0, flop_exec = 0;
   // optional per-kernel-class timing with HIP events on the launch stream (jamun_profile_*)
   unsigned prof_mask = 0;  // bit c: record HIP events around launches of profile class c
   int prof_every = 1;      // ... around every prof_every-th launch of the class (jamun_profile_sample)
@@ -259,36 +299,23 @@ void pack_edge_h16(jamun_sampler* s);                    // w1h_all / w1isc_all 
 // ---- jamun_plan.cpp -----------------------------------------------------------------------------
 void plan_tiles(const int32_t* ptr, const std::vector<int>& graph_of, int N, int cap, std::vector<int2>& t_atoms,
                 std::vector<int2>& t_span, std::vector<int>& t_chunk, int& n_chunks, int& span_max, bool& row_blocks);
-struct SegPlan {
-  std::vector<int4> segs;  // [cus][max_segs][2]
-  int max_segs = 1, n_slabs = 1;
-  std::vector<int> atom_nslab;
-};
 SegPlan plan_segments(int cus, int ng, int n_k, int N, const std::vector<int2>& t_atoms, const std::vector<int>& t_chunk, int n_chunks,
                       const std::vector<int64_t>& tile_weight, const std::vector<char>* skip = nullptr, double seg_cost = 0.0);
-struct TilePlan {
-  std::vector<int2> atoms, span;  // per tile: {first destination atom, atoms}, {lo, hi} source atoms
-  std::vector<int> chunk;         // ... and its destination chunk (tiles of one chunk number their partial slabs jointly)
-  int n_chunks = 0, span_max = 0;
-  bool row_blocks = false;        // a molecule's sources were cut into row blocks
-};
-// What select_kernels decides; jamun_sampler_create uploads it and sizes the work buffers by it.  Below conv_path the fields are
-// meaningful for CONV_DG only.
-struct KernelPlan {
-  ConvPath conv_path = CONV_GENERAL;
-  InitPath init_path = INIT_GENERAL;
-  int dg_mode = 0, dg_emu = 1, dg_RS = 0;
-  TilePlan tiles;
-  int ng = 1;
-  double seg_cost = 0.0;
-  SegPlan segs, init_segs;     // work lists of the hidden layers; of the initial projector when it keeps lists of its own (own_init_segs)
-  bool own_init_segs = false, init_tail = false;
-  std::vector<int4> tail_tiles;  // tail tiles (mode 4): records, destinations, runs of hidden units, bytes of the parked operands
-  std::vector<int> tail_atom;
-  int tail_runs = 0;
-  size_t tail_P_bytes = 0;
-  int mf_nks = 4, ml_window = 0, initv_nbuf = 2;
-};
 ConvPath base_conv_path(const jamun_hparams& hp, int n_emb);
-KernelPlan select_kernels(const jamun_hparams& hp, const jamun_tuning& tn, const jamun_topology& topo, const std::vector<int>& graph_of, int nmax,
-                          int S, int cus, ConvPath base, const std::vector<LayerDev>& layers, int n_uniq, bool have_atom_uid);
+// What check_topology derives from a topology on the host: walker of every atom; bonded edges by destination (CSR: pointers, sources);
+// atoms of the largest walker; the edge stride (32 radial slots + the largest bonded in-degree, at least 1)
+struct TopoHost { std::vector<int> graph_of, bip, bis; int nmax = 0, S = 1; };
+TopoHost check_topology(const jamun_topology& topo);
+// Which weight layouts packing produced (jamun_pack.cpp), as far as kernel selection asks: plain flags, filled from the sampler's layers
+struct PackedLayouts {
+  struct Hidden { bool dg, mf, tail; };  // a hidden layer's weights for k_conv_dg (DgDev::wx), k_conv_mf / k_conv_ml (wm), the tail tiles (wmt)
+  std::vector<Hidden> hidden;
+  bool tt2 = false, tabw = false, wx = false;  // initial projector: tables of k_conv_init_v / k_conv_mfi, weights of k_conv_mfx / k_conv_mlx
+  int tab_ut = 0, nt0 = 0;                     // ... LayerDev::tab_ut, p0.nt
+};
+KernelPlan select_kernels(const jamun_hparams& hp, const jamun_tuning& tn, const jamun_topology& topo, const TopoHost& th, int cus, ConvPath base,
+                          const PackedLayouts& lay, int n_uniq, bool have_atom_uid);
+// FLOP and byte constants of the hidden-layer kernels of a CONV_DG plan, per launch: the matrix-core FLOPs of the conv kernel (tail tiles run
+// in their own kernels), of the T pre-pass, and the bytes of the weight stream
+struct ConvModel { int64_t conv_flop = 0, tprod_flop = 0, weight_bytes = 0; };
+ConvModel conv_model(const KernelPlan& plan, const jamun_hparams& hp, int n_atoms);

@@ -333,6 +333,60 @@ def plan_segments(cus: int, ng: int, n_k: int, n_atoms: int, tile_atoms, tile_ch
     return {"segs": segs, "max_segs": ms.value, "n_slabs": nsl.value, "atom_nslab": nslab[:n_atoms].copy()}
 
 
+SELECT_KEYS = ("conv_path", "dg_mode", "init_path", "dg_emu", "dg_RS", "S", "n_tiles", "span_max", "row_blocks", "n_tail_tiles", "n_tail", "tail_runs",
+               "init_tail", "own_init_segs", "mf_nks", "ml_window", "initv_nbuf", "ng", "seg_cost_tenths", "max_segs", "n_slabs",
+               "conv_flop_exec_launch", "init_max_segs", "init_n_slabs")
+SELECT_LISTS = ("segs", "init_segs", "tail_tiles", "tiles", "atom_nslab", "init_atom_nslab", "chunk")
+
+
+def select_kernels(hp: dict, tuning: Optional[dict], ptr, bonds, cus: int, n_uniq: int, have_atom_uid: bool, hidden, layer0, lists=()) -> dict:
+    """``jamun_debug_select_kernels``: the kernel selection of jamun_sampler_create, run on the host (no GPU needed).  hp: fields of
+    ``jamun_hparams`` (the ones left out are zero; selection reads the widths, n_layers, edge_attr_dim, emb_dim and separable); tuning: switches
+    as for ``NativeSampler`` (``TUNING`` is not applied); ptr [n_graphs + 1]; bonds [2, n_bonds]; hidden: per hidden layer (dg, mf, tail)
+    flags; layer0: (tt2, tabw, tab_ut, wx, nt0).  Returns {name: int for SELECT_KEYS} plus the int32 arrays named in ``lists``
+    (SELECT_LISTS; segs / init_segs [cus, max_segs, 2, 4], tail_tiles / tiles [n, 4])."""
+    lib = _lib.load()
+    h = _lib.jamun_hparams()
+    for k, v in hp.items():
+        if k == "emb_dim":
+            for i in range(4):
+                h.emb_dim[i] = int(v[i])
+        else:
+            setattr(h, k, v)
+    t = _lib.jamun_tuning()
+    for k, v in (tuning or {}).items():
+        setattr(t, k, int(v))
+    p = np.ascontiguousarray(ptr, dtype=np.int32)
+    b = np.ascontiguousarray(bonds, dtype=np.int64).reshape(2, -1)
+    bs, bd = np.ascontiguousarray(b[0]), np.ascontiguousarray(b[1])
+    topo = _lib.jamun_topology()
+    topo.n_atoms, topo.n_graphs, topo.n_bonds = int(p[-1]), p.size - 1, bs.size
+    topo.ptr = p.ctypes.data_as(C.POINTER(C.c_int32))
+    topo.bond_src, topo.bond_dst = bs.ctypes.data_as(C.POINTER(C.c_int64)), bd.ctypes.data_as(C.POINTER(C.c_int64))
+    hid = np.ascontiguousarray([int(d) | int(m) << 1 | int(tl) << 2 for d, m, tl in hidden], dtype=np.int32)
+    l0 = np.ascontiguousarray([int(x) for x in layer0], dtype=np.int32)
+    out = np.zeros(len(SELECT_KEYS), dtype=np.int64)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    n = C.c_int64()
+
+    def call(which, buf):
+        _lib.check(lib.jamun_debug_select_kernels(C.byref(h), C.byref(t), C.byref(topo), int(cus), int(n_uniq), int(bool(have_atom_uid)), hid.size,
+                                                  vp(hid), vp(l0), vp(out), which, None if buf is None else vp(buf), 0 if buf is None else buf.size, C.byref(n)))
+
+    call(-1, None)
+    res = {k: int(out[i]) for i, k in enumerate(SELECT_KEYS)}
+    for name in lists:
+        which = SELECT_LISTS.index(name)
+        call(which, None)
+        buf = np.zeros(max(n.value, 1), dtype=np.int32)
+        call(which, buf)
+        buf = buf[: n.value]
+        if which in (0, 1):
+            buf = buf.reshape(int(cus), -1, 2, 4) if buf.size else buf.reshape(0, 0, 2, 4)
+        res[name] = buf.reshape(-1, 4) if which in (2, 3) else buf
+    return res
+
+
 def live_allocations() -> tuple:
     """``jamun_debug_live_allocations``: (number, bytes) of the device and pinned buffers the library holds in this process."""
     n, b = C.c_int64(), C.c_int64()

@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import _select_cases as sel
 import _sepconv_cases as sp
 from jamun_amd import native, synth
 
@@ -16,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
 SIGMA = sp.SIGMA
-WIDE_ARCH = dict(irreps_hidden="160x0e + 48x1e")  # ``h160x48`` of test_gpu_wide.py
+WIDE_ARCH = sel.WIDE_ARCH_H160  # ``h160x48`` of test_gpu_wide.py
 SKIP_KEY = "g.skip_connections.0.weights.scale_predictor.0.weight"  # read between build_layer and the layer's place in the sampler
 RADIAL_KEY = "g.layers.0.gated_conv.f.f.radial_nn.3.weight"  # read inside build_layer, after the node-update weights were uploaded
 
@@ -43,7 +44,7 @@ def _model(kind, without=None):
 def _batch(mols_kind):
     from jamun_amd.data import WalkerBatch
 
-    mols = [synth.random_chain(70, seed=0)] * 2 if mols_kind == "chain70x2" else sp.molecules(mols_kind)
+    mols = sel.molecules(mols_kind)
     return WalkerBatch.from_molecules(list(mols)).to(DEV)
 
 
@@ -56,15 +57,7 @@ def _y(mols_kind="ag4"):
     return pos + SIGMA * torch.randn(pos.shape, generator=torch.Generator().manual_seed(5)).to(DEV)
 
 
-ROUND_TRIPS = {  # name -> (model, molecules, tuning, what the stats must say so that the case is the path it names)
-    "default": ("conv", "ag4", None, lambda st: st["conv_path"] == 2),
-    "no_dg": ("conv", "ag4", {"no_dg": 1}, lambda st: st["conv_path"] == 0 and st["dg_mode"] == -1),
-    "separable": ("separable", "ag4", None, sp.is_separable),
-    "wide": ("wide", "ag4", None, lambda st: st["conv_path"] == 3),
-    "selfcheck_off": ("conv", "ag4", {"selfcheck": -1}, lambda st: st["conv_path"] == 2),
-    "mode5": ("conv", "chain70x2", None, lambda st: st["dg_mode"] == 5),
-    "tail_tiles": ("conv", "doubled_bonds", None, lambda st: st["dg_mode"] == 4 and st["n_tail_tiles"] > 0),
-}
+ROUND_TRIPS = sel.ROUND_TRIPS  # name -> (model, molecules, tuning, what the stats must say so that the case is the path it names)
 
 
 @pytest.mark.parametrize("name", list(ROUND_TRIPS))

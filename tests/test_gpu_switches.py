@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 import torch
 
+import _select_cases as sel
 import _switch_cases as sc
 from _switch_cases import RMSD_TOL_NM, SIGMA, rmsd
 
@@ -72,22 +73,12 @@ def _check_forward(smp, y, x_ref, inter, hp, sigma=SIGMA, bound=RMSD_TOL_NM):
     return x
 
 
-# (name, jamun_tuning, what jamun_sampler_stats must report) for a Conv checkpoint of the default widths
-def _default_kernels(st):
-    return st["conv_path"] == 2 and st["dg_mode"] in (4, 5) and st["dg_emu"] == 1
-
-
-CONV_SELECTIONS = [
-    ("default", None, _default_kernels),
-    ("no_dg", {"no_dg": 1}, lambda st: st["conv_path"] == 0 and st["init_path"] == 0),
-    ("no_mf", {"no_mf": 1}, lambda st: st["conv_path"] == 2 and st["dg_mode"] != 4),
-]
+# (name, jamun_tuning, what jamun_sampler_stats must report) per architecture: _select_cases.py, which tests/test_select_host.py asks of the
+# host selection as well
 ARCH = {  # name -> (keyword arguments of sc.checkpoint, selections)
-    "conv": (dict(), CONV_SELECTIONS),
-    "separable": (dict(separable=True), [("separable", None, lambda st: st["conv_path"] == 0 and st["dg_mode"] == -1)]),
-    # test_gpu_wide.py's H32 preset: a radial size outside the compiled kernels' envelope
-    "wide": (dict(arch_over=dict(edge_attr_dim=32)),
-             [("wide", None, lambda st: (st["conv_path"], st["init_path"], st["dg_mode"], st["dg_emu"]) == (3, 6, -1, 0))]),
+    "conv": (dict(), sel.CONV_SELECTIONS),
+    "separable": (dict(separable=True), sel.SEPARABLE_SELECTIONS),
+    "wide": (dict(arch_over=sel.WIDE_ARCH_H32), sel.WIDE_SELECTIONS),
 }
 
 
@@ -189,17 +180,7 @@ def test_sequence_index_outside_the_table_is_refused():
     assert torch.isfinite(_sampler(_model(sc.checkpoint()), mols).xhat(mols[0]["pos"].to(DEV))).all()
 
 
-SIGN_CASES = [  # (molecules, architecture, [(name, tuning, stats predicate)])
-    ("chain17x6", "conv", [
-        ("k_conv_mf + k_conv_mfi", None, lambda st: st["dg_mode"] == 4 and st["init_path"] == 3 and st["n_tail_tiles"] == 0),
-        ("k_conv_dg + k_conv_init_v", {"no_mf": 1, "no_mfi": 1}, lambda st: st["conv_path"] == 2 and st["dg_mode"] in (0, 1, 2, 3) and st["init_path"] == 2),
-        ("k_conv", {"no_dg": 1}, lambda st: st["conv_path"] == 0 and st["init_path"] == 0)]),
-    ("ragged", "conv", [("k_conv_mf + k_conv_mfx", None, lambda st: st["dg_mode"] == 4 and st["init_path"] == 4)]),
-    ("chain33x4", "conv", [("k_tail_form / k_tail_contract", None, lambda st: st["dg_mode"] == 4 and st["n_tail_tiles"] >= 4)]),
-    ("chig93x2", "conv", [("k_conv_ml + k_conv_mlx", None, lambda st: st["dg_mode"] == 5 and st["init_path"] == 5)]),
-    ("chain17x6", "separable", ARCH["separable"][1]),
-    ("chain17x6", "wide", ARCH["wide"][1]),
-]
+SIGN_CASES = sel.FAMILY_CASES  # (molecules, architecture, [(name, tuning, stats predicate)])
 
 
 @pytest.mark.parametrize("kind,arch,selections", SIGN_CASES, ids=[f"{k}-{a}" for k, a, _ in SIGN_CASES])
@@ -238,7 +219,7 @@ def test_forward_over_the_noise_levels(kind, sigma):
     mols, ck = sc.molecules(kind), sc.checkpoint()
     y, x_ref, inter, hp = _oracle(mols, ck, sigma=sigma)
     smp = _sampler(_model(ck), mols, sigma=sigma)
-    assert _default_kernels(smp.stats()), smp.stats()
+    assert sel.default_kernels(smp.stats()), smp.stats()
     _check_forward(smp, y, x_ref, inter, hp, sigma=sigma, bound=sc.xhat_bound(kind, sigma))
     if kind == "dense70":
         assert int(torch.bincount(inter["edge_index"][1]).max()) >= 32

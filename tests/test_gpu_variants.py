@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+import _select_cases as sel
+
 pytestmark = pytest.mark.gpu
 
 RMSD_TOL_NM = 1e-5
@@ -33,20 +35,21 @@ def rmsd(a, b):
     return ((a.double().cpu() - b.double().cpu()) ** 2).sum(-1).mean().sqrt().item()
 
 
-# (variant, molecules, what jamun_sampler_stats must report — the kernels the case is meant to exercise)
+# (variant, molecules, what jamun_sampler_stats must report — the kernels the case is meant to exercise; the default-width ones in
+# _select_cases.py, where tests/test_select_host.py asks the host selection the same)
 CASES = [
-    ("nl2", "ragged", dict(dg_mode=4, dg_emu=1)),
+    ("nl2", "ragged", sel.VARIANT_STATS["nl2", "ragged"]),
     ("sep_nl4", "ragged", dict()),
     ("idrome", "ragged", dict(dg_emu=1)),
     ("idrome", "dense70", dict(dg_emu=1)),
     ("r1000", "ragged", dict(dg_emu=1)),
     ("h64x16", "ragged", dict()),
-    ("trained", "chain17x6", dict(dg_mode=4, init_path=3, dg_emu=1)),
-    ("trained", "ragged", dict(dg_mode=4, init_path=4, dg_emu=1)),
-    ("trained", "chig93x2", dict(dg_mode=5, init_path=5, dg_emu=1, ml_window=96)),  # the reference's chignolin shape (93 heavy atoms) on k_conv_ml / k_conv_mlx
+    ("trained", "chain17x6", sel.VARIANT_STATS["trained", "chain17x6"]),
+    ("trained", "ragged", sel.VARIANT_STATS["trained", "ragged"]),
+    ("trained", "chig93x2", sel.VARIANT_STATS["trained", "chig93x2"]),  # the reference's chignolin shape (93 heavy atoms) on k_conv_ml / k_conv_mlx
     ("sep_trained", "ragged", dict()),
     # the default point on BASELINE configs[1] as the reference runs it: 48 DISTINCT dipeptides (real topology, 143 distinct embedding rows)
-    ("default", "dipep48", dict(dg_mode=4, dg_emu=1, init_path=4)),
+    ("default", "dipep48", sel.VARIANT_STATS["default", "dipep48"]),
 ]
 
 
