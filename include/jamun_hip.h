@@ -374,6 +374,51 @@ int jamun_autocov_sums_work(int32_t n_frames, int32_t max_lag, int64_t* n_double
 int jamun_autocov_sums(const double* y_dev, int64_t stride, int32_t n_frames, int32_t max_lag, double* out_dev, double* work_dev, int64_t work_capacity,
                        void* stream);
 
+/* ---- k-means and Markov state model counts of a projected trajectory (jamun_msm.hip) --------------------------------------------------------
+ * The reductions over frames behind the reference's compute_MSM_stats (analysis/utils.py: pyemma's k-means, Markov state model and PCCA+);
+ * Lloyd's loop, the estimators and PCCA are the host's (jamun_amd/msm.py).  y_dev is fp64 [n_frames] rows of d values, row_stride (>= d)
+ * doubles apart: the output of jamun_project_frames, read in place.  1 <= k <= 1024, 1 <= d <= 128, k d <= 16384, 1 <= n_states <= 1024.
+ *
+ * jamun_assign_centers: centers_dev fp64 [k][d] (finite) -> labels_dev int32 [n_frames], the centre of smallest squared distance, the
+ * lowest index on a tie.  The distance is  acc = +0.0;  for j ascending:  diff = y[j] - c[j];  sq = diff * diff;  acc = acc + sq  with
+ * each of the three operations rounded on its own (no fused multiply-add), so label and distance equal the numpy loop of
+ * msm.assign_centers_host bit for bit.  sqdist_dev (fp64 [n_frames], or NULL) receives the distance to the chosen centre.  A row with a
+ * non-finite value gets label -1 and sqdist NaN; no other row is touched by it.  prev_labels_dev (int32 [n_frames]) and n_changed_dev
+ * (one int64, ZEROED BY THE CALLER) go together or are both NULL: the number of frames whose label differs from prev_labels_dev is
+ * ADDED to *n_changed_dev by integer atomics.  prev_labels_dev may be labels_dev itself.
+ *
+ * jamun_cluster_sums: labels_dev int32 [n_frames] -> counts_dev int64 [k], the rows that carry each label, and sums_dev fp64 [k][d], their
+ * sum.  Labels outside [0, k) are skipped (-1 included).  Additions only, in a fixed order: the frames are cut into slices of 1024; within
+ * a slice a cluster's rows are added in ascending frame order onto +0.0 (work_dev [slices][k d + k] doubles, jamun_cluster_sums_work); the
+ * slices are added in ascending order onto +0.0.  msm.cluster_sums_host adds in the same order: the result equals it bit for bit and is
+ * the same in every run.  With d = 1 on the sqdist of jamun_assign_centers it gives the inertia of every cluster.
+ *
+ * jamun_transition_counts: labels_dev int32 [n_frames], lag >= 1, map_dev int32 [n_in] or NULL -> counts_dev int64 [n_states][n_states],
+ * ZEROED BY THE CALLER: counts[a][b] is INCREASED by the number of t < n_frames - lag with state(t) = a and state(t + lag) = b (sliding
+ * counts; the counts of several chains add up and no pair crosses from one chain into the next).  state(t) is map[label] with a map
+ * (n_in >= 1 entries, -1 for none) and the label itself without one (n_in is then ignored and taken as n_states); a pair is skipped when
+ * a label is negative or >= n_in, or a state is outside [0, n_states).  lag >= n_frames counts nothing and succeeds.
+ *
+ * jamun_label_counts: the same labels and map, bounds_dev int32 [n_seg + 1] (non-decreasing, within [0, n_frames]; 1 <= n_seg <= 4096) ->
+ * counts_dev int64 [n_seg][n_states], ZEROED BY THE CALLER: counts[s][a] is INCREASED by the number of frames bounds[s] <= t < bounds[s+1]
+ * in state a.  Frames before bounds[0] or from bounds[n_seg] on count nowhere; bounds that do not ascend give counts that mean nothing but
+ * never a write outside the table.
+ *
+ * The counts are integer atomics: exact in any order of arrival.  No floating-point atomics.  A negative count or stride, k, d, k d,
+ * n_states or n_seg outside its range, row_stride < d, lag < 1, n_in < 1 with a map, work_capacity (in doubles) below the need, one of
+ * prev_labels_dev / n_changed_dev without the other, or a NULL pointer that is needed is JAMUN_ERR_INVALID and nothing is written;
+ * n_frames == 0 launches nothing, writes nothing and succeeds (the ranges are checked first).  Caller-owned buffers, work queued on
+ * `stream`, no synchronisation, no allocation. */
+int jamun_assign_centers(const double* y_dev, int64_t row_stride, int32_t n_frames, int32_t d, const double* centers_dev, int32_t k,
+                         int32_t* labels_dev, double* sqdist_dev, const int32_t* prev_labels_dev, int64_t* n_changed_dev, void* stream);
+int jamun_cluster_sums_work(int32_t n_frames, int32_t d, int32_t k, int64_t* n_doubles);
+int jamun_cluster_sums(const double* y_dev, int64_t row_stride, int32_t n_frames, int32_t d, const int32_t* labels_dev, int32_t k,
+                       int64_t* counts_dev, double* sums_dev, double* work_dev, int64_t work_capacity, void* stream);
+int jamun_transition_counts(const int32_t* labels_dev, int32_t n_frames, int32_t lag, const int32_t* map_dev, int32_t n_in, int32_t n_states,
+                            int64_t* counts_dev, void* stream);
+int jamun_label_counts(const int32_t* labels_dev, int32_t n_frames, const int32_t* map_dev, int32_t n_in, int32_t n_states,
+                       const int32_t* bounds_dev, int32_t n_seg, int64_t* counts_dev, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

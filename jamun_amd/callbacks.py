@@ -559,6 +559,22 @@ class TICAMetricsCallback(TrajectoryMetricCallback):
         super().__init__(datasets, functools.partial(TICAMetrics, **kw))
 
 
+class MSMMetricsCallback(TrajectoryMetricCallback):
+    """`TrajectoryMetricCallback` over `msm.MSMMetrics` (the Markov-state-model part of the reference's ``analysis/run_analysis.py``:
+    ``compute_MSM_stats``): k-means, a Markov state model and its metastable states fitted on the TICA projection of the true trajectory;
+    per chain and for the joined trajectory the occupancies of the metastable states, their Jensen-Shannon distance from the true ones
+    (also against the number of samples) and the transition counts and matrix at ``traj_lag``, under ``<output_dir>/<label>/msm/``.
+    Keyword arguments go to the meter (``k``, ``max_iter``, ``seed``, ``msm_lag``, ``n_metastable``, ``traj_lag``, ``n_steps``, ``lag``,
+    ``features``, ``var_cutoff``, ``epsilon``, ``kinetic_map``, ``reference``, ``device``, ``output_dir``, ``sample_key``)."""
+
+    def __init__(self, datasets: Sequence, **kw):
+        import functools
+
+        from .msm import MSMMetrics
+
+        super().__init__(datasets, functools.partial(MSMMetrics, **kw))
+
+
 class MeasureSamplingTimeCallback:
     """Wall time per batch and per sampled conformation (one saved (walker, frame) pair — the reference's unit,
     ``callbacks/sampler/_measure_sampling_time.py:57,71``).  Writes ``sampler/timing.json`` on rank 0."""

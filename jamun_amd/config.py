@@ -38,6 +38,7 @@ TARGET_ALIASES = {
     "jamun.callbacks.sampler.RamachandranPlotMetricsCallback": "jamun_amd.callbacks.RamachandranMetricsCallback",
     "jamun.callbacks.sampler.ChemicalValidityMetricsCallback": "jamun_amd.callbacks.ChemicalValidityMetricsCallback",
     "jamun.callbacks.sampler.TICAMetricsCallback": "jamun_amd.callbacks.TICAMetricsCallback",
+    "jamun.callbacks.sampler.MSMMetricsCallback": "jamun_amd.callbacks.MSMMetricsCallback",
     "jamun.sampling.walkjump.MeasurementDependentParametersCallback": "jamun_amd.sampling.MeasurementDependentParametersCallback",
     "jamun.sampling.walkjump.InterpolateParametersCallback": "jamun_amd.sampling.InterpolateParametersCallback",
     "jamun.utils.ModelSamplingWrapper": "jamun_amd.sampling.ModelSamplingWrapper",

@@ -1,7 +1,8 @@
 // jamun_frames.cpp — the C entries that encode or analyse frames of a trajectory and never touch a jamun_sampler: the PDB / DCD encoders
 // (jamun_traj.hip), superposition (jamun_superpose.hip), internal coordinates (jamun_intcoord.hip), histograms of angle pairs with their
-// Jensen-Shannon divergence (jamun_hist.hip), chemical validity (jamun_validity.hip) and the reductions behind TICA: lagged moments,
-// projection, autocovariance sums (jamun_tica.hip).  Every refusal is raised before any HIP call.
+// Jensen-Shannon divergence (jamun_hist.hip), chemical validity (jamun_validity.hip), the reductions behind TICA: lagged moments,
+// projection, autocovariance sums (jamun_tica.hip), and those behind k-means and the Markov state model: nearest centres, cluster sums,
+// transition and occupancy counts (jamun_msm.hip).  Every refusal is raised before any HIP call.
 // The order of an entry's checks decides which message a caller with two faults sees, and the entries differ in it on purpose: where a
 // shared check below would change an order or a text, the entry keeps a line of its own.  Every entry's checks read top to bottom.
 #include "jamun_host.h"
@@ -48,6 +49,25 @@ void check_tica_lag(int32_t lag, int32_t n_frames) {
 void check_tica_acf_lag(int32_t max_lag) {
   if (max_lag < 0 || max_lag > JAMUN_TICA_MAX_ACF_LAG)
     throw Err(JAMUN_ERR_INVALID, "max_lag " + std::to_string(max_lag) + " is outside [0, " + std::to_string(JAMUN_TICA_MAX_ACF_LAG) + "]");
+}
+
+void check_range(const char* name, int64_t v, int64_t lo, int64_t hi) {
+  if (v < lo || v > hi)
+    throw Err(JAMUN_ERR_INVALID, std::string(name) + " " + std::to_string(v) + " is outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+}
+
+void check_centers(int32_t k, int32_t d) {
+  check_range("k", k, 1, JAMUN_MSM_MAX_K);
+  check_range("d", d, 1, JAMUN_MSM_MAX_D);
+  if ((int64_t)k * d > JAMUN_MSM_MAX_KD)
+    throw Err(JAMUN_ERR_INVALID, "k * d = " + std::to_string((int64_t)k * d) + " is above " + std::to_string(JAMUN_MSM_MAX_KD));
+}
+
+// the states of a count table and the table the labels go through first; returns the number of labels taken
+int32_t check_states(int32_t n_states, const int32_t* map_dev, int32_t n_in) {
+  check_range("n_states", n_states, 1, JAMUN_MSM_MAX_STATES);
+  if (map_dev && n_in < 1) throw Err(JAMUN_ERR_INVALID, "n_in " + std::to_string(n_in) + " is below 1: a map has at least one entry");
+  return map_dev ? n_in : n_states;
 }
 
 constexpr int64_t kMaxModel = 1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
@@ -276,6 +296,73 @@ int jamun_autocov_sums(const double* y_dev, int64_t stride, int32_t n_frames, in
     require_capacity("work_capacity", work_capacity, autocov_work_doubles(n_frames, max_lag), "partial sums", "doubles");
     if (!y_dev || !out_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
     launch_autocov_sums(y_dev, stride, n_frames, max_lag, out_dev, work_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- nearest centres, cluster sums, transition and occupancy counts (jamun_msm.hip) ------------------------------------------------------------
+
+int jamun_assign_centers(const double* y_dev, int64_t row_stride, int32_t n_frames, int32_t d, const double* centers_dev, int32_t k,
+                         int32_t* labels_dev, double* sqdist_dev, const int32_t* prev_labels_dev, int64_t* n_changed_dev, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_centers(k, d);
+    if (row_stride < d) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below d = " + std::to_string(d));
+    if ((prev_labels_dev == nullptr) != (n_changed_dev == nullptr))
+      throw Err(JAMUN_ERR_INVALID, "prev_labels_dev and n_changed_dev go together: one of them is null");
+    if (n_frames == 0) return;  // (nothing to write)
+    if (!y_dev || !centers_dev || !labels_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_assign_centers(y_dev, row_stride, n_frames, d, centers_dev, k, labels_dev, sqdist_dev, prev_labels_dev, (long long*)n_changed_dev,
+                          (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_cluster_sums_work(int32_t n_frames, int32_t d, int32_t k, int64_t* n_doubles) {
+  return guarded([&] {
+    if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_centers(k, d);
+    *n_doubles = n_frames == 0 ? 0 : cluster_work_doubles(n_frames, d, k);
+  });
+}
+
+int jamun_cluster_sums(const double* y_dev, int64_t row_stride, int32_t n_frames, int32_t d, const int32_t* labels_dev, int32_t k,
+                       int64_t* counts_dev, double* sums_dev, double* work_dev, int64_t work_capacity, void* stream) {
+  return guarded([&] {
+    if (row_stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    check_centers(k, d);
+    if (row_stride < d) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below d = " + std::to_string(d));
+    if (n_frames == 0) return;  // (nothing to write)
+    require_capacity("work_capacity", work_capacity, cluster_work_doubles(n_frames, d, k), "partial sums", "doubles");
+    if (!y_dev || !labels_dev || !counts_dev || !sums_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_cluster_sums(y_dev, row_stride, n_frames, d, labels_dev, k, (long long*)counts_dev, sums_dev, work_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_transition_counts(const int32_t* labels_dev, int32_t n_frames, int32_t lag, const int32_t* map_dev, int32_t n_in, int32_t n_states,
+                            int64_t* counts_dev, void* stream) {
+  return guarded([&] {
+    if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    const int32_t n_labels = check_states(n_states, map_dev, n_in);
+    if (lag < 1) throw Err(JAMUN_ERR_INVALID, "lag " + std::to_string(lag) + " is below 1");
+    if (lag >= n_frames) return;  // (no frames, or no pair that far apart: nothing to count)
+    if (!labels_dev || !counts_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_transition_counts(labels_dev, n_frames, lag, map_dev, n_labels, n_states, (long long*)counts_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_label_counts(const int32_t* labels_dev, int32_t n_frames, const int32_t* map_dev, int32_t n_in, int32_t n_states,
+                       const int32_t* bounds_dev, int32_t n_seg, int64_t* counts_dev, void* stream) {
+  return guarded([&] {
+    if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
+    const int32_t n_labels = check_states(n_states, map_dev, n_in);
+    check_range("n_seg", n_seg, 1, JAMUN_MSM_MAX_SEGMENTS);
+    if (n_frames == 0) return;  // (nothing to count)
+    if (!labels_dev || !bounds_dev || !counts_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_label_counts(labels_dev, n_frames, map_dev, n_labels, n_states, bounds_dev, n_seg, (long long*)counts_dev, (hipStream_t)stream);
     HIPCHECK(hipGetLastError());
   });
 }

@@ -546,3 +546,18 @@ void launch_lagged_moments(const float* x, long long row_stride, int n_frames, i
 void launch_project_frames(const float* x, long long row_stride, int n_frames, int width, const double* mean, const double* v, int d, double* out,
                            hipStream_t st);
 void launch_autocov_sums(const double* y, long long stride, int n_frames, int max_lag, double* out, double* work, hipStream_t st);
+// jamun_msm.hip — nearest centre of every row of a projection, sums of the rows of every cluster (in the fixed order of the TICA reductions:
+// slices of JAMUN_TICA_SLICE frames), transition counts at a lag and occupancy counts over segments of frames; n_frames >= 1
+#define JAMUN_MSM_MAX_K 1024         // centres (native.MSM_MAX_K mirrors it)
+#define JAMUN_MSM_MAX_D 128          // columns of a row (native.MSM_MAX_D)
+#define JAMUN_MSM_MAX_KD 16384       // k * d at most (native.MSM_MAX_KD)
+#define JAMUN_MSM_MAX_STATES 1024    // states of the count tables (native.MSM_MAX_STATES)
+#define JAMUN_MSM_MAX_SEGMENTS 4096  // segments of jamun_label_counts (native.MSM_MAX_SEGMENTS)
+long long cluster_work_doubles(int n_frames, int d, int k);
+void launch_assign_centers(const double* y, long long row_stride, int n_frames, int d, const double* centers, int k, int* labels, double* sqdist,
+                           const int* prev, long long* n_changed, hipStream_t st);
+void launch_cluster_sums(const double* y, long long row_stride, int n_frames, int d, const int* labels, int k, long long* counts, double* sums,
+                         double* work, hipStream_t st);
+void launch_transition_counts(const int* labels, int n_frames, int lag, const int* map, int n_in, int n_states, long long* counts, hipStream_t st);  // (lag < n_frames)
+void launch_label_counts(const int* labels, int n_frames, const int* map, int n_in, int n_states, const int* bounds, int n_seg, long long* counts,
+                         hipStream_t st);

@@ -997,3 +997,176 @@ def autocov_sums(y: torch.Tensor, max_lag: int, out: Optional[torch.Tensor] = No
         work = _tica_workspace(dev, need.value)
         _lib.check(lib.jamun_autocov_sums(_ptr(y), int(y.stride(0)) if T > 1 else 1, T, max_lag, _ptr(out), _ptr(work), int(work.numel()), _stream()))
     return out
+
+
+# ---- nearest centres, cluster sums, transition and occupancy counts (jamun_msm.hip) ----------------------------------------------------------
+
+MSM_MAX_K = 1024         # centres `assign_centers` and `cluster_sums` take (JAMUN_MSM_MAX_K, jamun_internal.h)
+MSM_MAX_D = 128          # columns of a row (JAMUN_MSM_MAX_D)
+MSM_MAX_KD = 16384       # k * d at most (JAMUN_MSM_MAX_KD)
+MSM_MAX_STATES = 1024    # states of the count tables (JAMUN_MSM_MAX_STATES)
+MSM_MAX_SEGMENTS = 4096  # segments of `label_counts` (JAMUN_MSM_MAX_SEGMENTS)
+
+
+def check_centers_shape(k: int, d: int) -> None:
+    """The limits of the device path on ``k`` centres of ``d`` columns (``ValueError`` otherwise), before anything needs a GPU."""
+    if not (1 <= k <= MSM_MAX_K and 1 <= d <= MSM_MAX_D and k * d <= MSM_MAX_KD):
+        raise ValueError(f"k = {k} centres of d = {d} columns: the device path takes 1 <= k <= {MSM_MAX_K}, 1 <= d <= {MSM_MAX_D} and "
+                         f"k * d <= {MSM_MAX_KD} (the host functions of jamun_amd.msm have no limit)")
+
+
+def _projection_shape(y) -> Tuple[int, int]:
+    """The shape rule of the rows `assign_centers` and `cluster_sums` read, before anything needs a GPU: ``[T, d]`` with ``1 <= d <= 128``."""
+    if not torch.is_tensor(y) or y.ndim != 2:
+        raise ValueError(f"y must be a [frames, d] tensor, got {tuple(getattr(y, 'shape', ()))}")
+    T, d = int(y.shape[0]), int(y.shape[1])
+    if not 1 <= d <= MSM_MAX_D:
+        raise ValueError(f"{d} columns: the device path takes 1 to {MSM_MAX_D}")
+    return T, d
+
+
+def _projection_rows(y, T: int, d: int) -> int:
+    """``RuntimeError`` unless ``y`` is float64 on a GPU with adjacent columns; returns the row stride in doubles."""
+    if not y.is_cuda or y.dtype != torch.float64 or (d > 1 and y.stride(1) != 1) or (T > 1 and y.stride(0) < d):
+        raise RuntimeError(f"y must be a float64 tensor on the GPU with adjacent columns, got {y.dtype} {tuple(y.shape)} strides {tuple(y.stride())} "
+                           f"on {y.device}")
+    _fit_31_bits(f"{T} frames: the count must fit 31 bits", T)
+    return int(y.stride(0)) if T > 1 else d
+
+
+def _labels(name: str, labels, device=None, T: Optional[int] = None) -> torch.Tensor:
+    if (not torch.is_tensor(labels) or labels.ndim != 1 or labels.dtype != torch.int32 or not labels.is_cuda or not labels.is_contiguous()
+            or (device is not None and labels.device != device) or (T is not None and int(labels.shape[0]) != T)):
+        raise RuntimeError(f"{name} must be a contiguous int32 [{'frames' if T is None else T}] tensor on the GPU"
+                           f"{'' if device is None else f' ({device})'}, got {getattr(labels, 'dtype', None)} {tuple(getattr(labels, 'shape', ()))} "
+                           f"on {getattr(labels, 'device', None)}")
+    _fit_31_bits(f"{labels.shape[0]} frames: the count must fit 31 bits", int(labels.shape[0]))
+    return labels
+
+
+def assign_centers(y: torch.Tensor, centers, labels: Optional[torch.Tensor] = None, sqdist=None, prev_labels: Optional[torch.Tensor] = None,
+                   n_changed: Optional[torch.Tensor] = None):
+    """Queue the nearest centre of every row of ``y [T, d]`` (device float64 with adjacent columns: what `project_frames` returns, or a
+    view of it with a row stride) on the current stream.  ``centers [k, d]`` float64 (a host array is uploaded, a tensor on the device is
+    used as it is).  Returns ``(labels int32 [T], sqdist float64 [T] or None, n_changed int64 [1] or None)``: the centre of smallest squared
+    distance (the lowest index on a tie; -1 and a NaN distance for a row with a non-finite value), the distance to it where ``sqdist`` is
+    ``True`` or a tensor to write to, and, with ``prev_labels`` (int32 ``[T]``), the number of labels that differ from it ADDED to
+    ``n_changed`` (default a new zero).  Label and distance equal `msm.assign_centers_host` bit for bit.  See ``jamun_assign_centers``."""
+    T, d = _projection_shape(y)
+    shape_c = tuple(getattr(centers, "shape", ()))
+    if len(shape_c) != 2 or shape_c[1] != d:
+        raise ValueError(f"centers must have shape [k, {d}], got {shape_c}")
+    k = int(shape_c[0])
+    check_centers_shape(k, d)
+    row_stride = _projection_rows(y, T, d)
+    dev = y.device
+    if not torch.is_tensor(centers):
+        centers = torch.from_numpy(np.ascontiguousarray(centers, dtype=np.float64))
+    if centers.dtype != torch.float64:
+        raise ValueError(f"centers must hold float64, got {centers.dtype}")
+    centers = centers.to(dev).contiguous()
+    if n_changed is not None and prev_labels is None:
+        raise ValueError("n_changed needs prev_labels to compare with")
+    lib = _lib.load()
+    labels = _result("labels", labels, (T,), torch.int32, dev)
+    if sqdist is True:
+        sqdist = torch.empty((T,), dtype=torch.float64, device=dev)
+    elif sqdist is False:
+        sqdist = None
+    elif sqdist is not None:
+        sqdist = _result("sqdist", sqdist, (T,), torch.float64, dev)
+    if prev_labels is not None:
+        prev_labels = _labels("prev_labels", prev_labels, dev, T)
+        n_changed = _result("n_changed", n_changed, (1,), torch.int64, dev, fill=0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_assign_centers(_ptr(y), row_stride, T, d, _ptr(centers), k, _ptr(labels), _ptr(sqdist), _ptr(prev_labels),
+                                            _ptr(n_changed), _stream()))
+    return labels, sqdist, n_changed
+
+
+def cluster_sums(y: torch.Tensor, labels: torch.Tensor, k: int, counts: Optional[torch.Tensor] = None,
+                 sums: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Queue the per-cluster sums of the rows ``y [T, d]`` (as `assign_centers` takes them; a ``[T]`` tensor counts as one column) on the
+    current stream: ``(counts int64 [k], sums float64 [k, d])``, the rows carrying each label of ``labels`` (int32 ``[T]``; labels outside
+    ``[0, k)`` are skipped) and their sum, added in the fixed order of `msm.cluster_sums_host`: the same bits as the host's, in every run.
+    The workspace is this module's (shared with the TICA reductions).  See ``jamun_cluster_sums``."""
+    if torch.is_tensor(y) and y.ndim == 1:
+        y = y[:, None]
+    T, d = _projection_shape(y)
+    if not _is_int(k):
+        raise ValueError(f"k must be an integer, got {k!r}")
+    k = int(k)
+    check_centers_shape(k, d)
+    row_stride = _projection_rows(y, T, d)
+    dev = y.device
+    labels = _labels("labels", labels, dev, T)
+    lib = _lib.load()
+    counts = _result("counts", counts, (k,), torch.int64, dev)
+    sums = _result("sums", sums, (k, d), torch.float64, dev)
+    need = C.c_int64()
+    _lib.check(lib.jamun_cluster_sums_work(T, d, k, C.byref(need)))
+    with torch.cuda.device(dev):
+        if T == 0:
+            counts.zero_()  # (no frame: the call writes nothing)
+            sums.zero_()
+        work = _tica_workspace(dev, need.value)
+        _lib.check(lib.jamun_cluster_sums(_ptr(y), row_stride, T, d, _ptr(labels), k, _ptr(counts), _ptr(sums), _ptr(work), int(work.numel()), _stream()))
+    return counts, sums
+
+
+def _state_map(state_map, n_states: int, dev) -> Tuple[Optional[torch.Tensor], int]:
+    if not _is_int(n_states) or not 1 <= int(n_states) <= MSM_MAX_STATES:
+        raise ValueError(f"n_states must be an integer in [1, {MSM_MAX_STATES}], got {n_states!r}")
+    if state_map is None:
+        return None, int(n_states)
+    if not torch.is_tensor(state_map):
+        state_map = torch.from_numpy(np.ascontiguousarray(state_map, dtype=np.int32))
+    if state_map.ndim != 1 or state_map.dtype != torch.int32 or state_map.shape[0] < 1:
+        raise ValueError(f"state_map must be a non-empty int32 [n_in] table, got {state_map.dtype} {tuple(state_map.shape)}")
+    _fit_31_bits("state_map: the length must fit 31 bits", int(state_map.shape[0]))
+    return state_map.to(dev).contiguous(), int(state_map.shape[0])
+
+
+def transition_counts(labels: torch.Tensor, lag: int, n_states: int, state_map=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the sliding transition counts of ``labels`` (device int32 ``[T]``) at ``lag >= 1`` on the current stream: int64
+    ``[n_states, n_states]``, ``out[a, b]`` INCREASED by the number of ``t < T - lag`` with ``state(t) = a`` and ``state(t + lag) = b``.
+    ``state_map`` (int32 ``[n_in]``, -1 for none; host array or device tensor) takes a label to its state; without it the label is the
+    state.  Pairs with a label or state out of range are skipped.  ``out`` (contiguous int64 of that shape on the device) is added to: hand
+    the same tensor in for every chain; default a new zero tensor.  `msm.transition_counts_host` is the specification."""
+    labels = _labels("labels", labels)
+    dev = labels.device
+    if not _is_int(lag) or int(lag) < 1:
+        raise ValueError(f"lag must be an integer of at least 1, got {lag!r}")
+    _fit_31_bits("lag must fit 31 bits", int(lag))
+    state_map, n_in = _state_map(state_map, n_states, dev)
+    n_states = int(n_states)
+    lib = _lib.load()
+    out = _result("out", out, (n_states, n_states), torch.int64, dev, fill=0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_transition_counts(_ptr(labels), int(labels.shape[0]), int(lag), _ptr(state_map), n_in, n_states, _ptr(out), _stream()))
+    return out
+
+
+def label_counts(labels: torch.Tensor, bounds, n_states: int, state_map=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the occupancy counts of ``labels`` (device int32 ``[T]``) over the segments ``bounds[s] <= t < bounds[s + 1]`` on the current
+    stream: int64 ``[n_seg, n_states]``, INCREASED by the frames of every segment in every state.  ``bounds`` int32 ``[n_seg + 1]``,
+    non-decreasing within ``[0, T]`` (a host array is checked and uploaded; a device tensor is taken as checked), ``state_map`` and
+    ``out`` as in `transition_counts`.  `msm.label_counts_host` is the specification."""
+    labels = _labels("labels", labels)
+    dev, T = labels.device, int(labels.shape[0])
+    state_map, n_in = _state_map(state_map, n_states, dev)
+    n_states = int(n_states)
+    if not _on_device(bounds):
+        b = np.asarray(bounds)
+        if b.ndim != 1 or b.shape[0] < 2 or not np.issubdtype(b.dtype, np.integer) or (np.diff(b) < 0).any() or b[0] < 0 or b[-1] > T:
+            raise ValueError(f"bounds must be at least two non-decreasing integers within [0, {T}], got {b.tolist() if b.size <= 16 else b.shape}")
+        bounds = np.ascontiguousarray(b, dtype=np.int32)
+    bounds = _table("bounds", "int32 [n_seg + 1]", bounds, _on_device(bounds), dev, torch.int32, (None,))
+    n_seg = int(bounds.shape[0]) - 1
+    if not 1 <= n_seg <= MSM_MAX_SEGMENTS:
+        raise ValueError(f"{n_seg} segments: the device path takes 1 to {MSM_MAX_SEGMENTS}")
+    lib = _lib.load()
+    out = _result("out", out, (n_seg, n_states), torch.int64, dev, fill=0)
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_label_counts(_ptr(labels), T, _ptr(state_map), n_in, n_states, _ptr(bounds), n_seg, _ptr(out), _stream()))
+    return out

@@ -20,7 +20,7 @@ Features: interleaved (cos, sin) pairs of phi and psi of every residue and, with
 ``add_backbone_torsions(cossin=True)`` and ``add_sidechain_torsions(cossin=True)`` give (`features.torsion_indices` without its omega rows,
 ``internal_coords(cossin=True)``).
 
-Out of scope: k-means and the Markov state model of ``compute_MSM_stats``, plots, wandb, histograms of the components on the device, and
+k-means and the Markov state model of ``compute_MSM_stats`` are `jamun_amd.msm`'s.  Out of scope: plots, wandb, histograms of the components on the device, and
 gathering chains across ranks (each rank meters its own walkers, as the other meters do).
 """
 
