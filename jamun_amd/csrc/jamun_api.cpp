@@ -787,6 +787,8 @@ static void sampler_self_check(const jamun_model* m, float sigma, const jamun_to
   for (size_t l = 0; l < s->layers.size(); ++l) compare(s->x[l], r->x[l], (size_t)n_cmp * s->XS, "node features after block ", (int)l);
   compare(s->g, r->g, (size_t)n_cmp * 3, "network output g, block ", (int)s->layers.size());
   if (s->dev.ml_count) { HIPCHECK(hipMemset(s->dev.ml_count, 0, sizeof(unsigned long long))); s->ml_launches = 0; }  // (the check's launches are not the run's)
+  // a device memset need not have finished when it returns: create is synchronous and leaves nothing pending, whatever stream comes first
+  HIPCHECK(hipDeviceSynchronize());
   s->edges_built = false;
 }
 void jamun_sampler_destroy(jamun_sampler* s) { delete s; }
