@@ -419,6 +419,52 @@ int jamun_transition_counts(const int32_t* labels_dev, int32_t n_frames, int32_t
 int jamun_label_counts(const int32_t* labels_dev, int32_t n_frames, const int32_t* map_dev, int32_t n_in, int32_t n_states,
                        const int32_t* bounds_dev, int32_t n_seg, int64_t* counts_dev, void* stream);
 
+/* ---- sliced Wasserstein distance of two clouds of descriptors (jamun_swd.hip) ---------------------------------------------------------------
+ * What the reference's compute_sliced_Wasserstein_distance_of_ramachandran (metrics/_ramachandran.py) gets from the `ot` package: both
+ * clouds projected on n_proj directions, per direction the 1-D Wasserstein distance at p = 2 with uniform weights (the clouds may differ
+ * in size), and (mean over directions of W2^2)^0.5, which the caller takes from the n_proj values.  jamun_amd/swd.py is the specification.
+ * 1 <= width <= 128, 1 <= n_proj <= 64, every count of frames or keys >= 1.
+ *
+ * jamun_swd_project: x_dev fp32 [n_frames] rows of `width` values, row_stride (>= width) floats apart, proj_dev fp32 [width][n_proj] ->
+ * out_dev fp32 [n_proj][n_frames],  out[l][t] = fl32(sum_j double(x[t][j]) * double(proj[j][l])),  the sum in fp64 onto +0.0 with j
+ * ascending, rounded to fp32 once.  A product of two promoted fp32 values is exact in fp64, so a fused and an unfused accumulate give the
+ * same bits: the result equals swd.project_host bit for bit.
+ *
+ * "Sorted" below means sorted by the order image of swd.order_image (fp32 -> uint32: all bits of a negative flipped, the sign bit of a
+ * non-negative set, every NaN sent to 0xFFFFFFFF): -0.0 < +0.0, NaN last and written as the quiet NaN 0x7FC00000.  A sorted column is
+ * unique as bits.
+ *
+ * jamun_swd_sort_segments: keys_dev fp32 [n_proj][n_frames] and 1 to 64 cuts (a HOST array, ascending strictly within [1, n_frames]) ->
+ * out_dev fp32 [n_proj][n_frames]: of every column the frames cuts[c-1] <= t < cuts[c] (cuts[-1] := 0) sorted, each segment on its own;
+ * frames from the last cut on are copied as they are.  OUT OF PLACE: tiles of 4096 keys are sorted in LDS, then merge-path passes
+ * alternate between out_dev and work_dev (jamun_swd_sort_work floats: n_proj * n_frames when a segment is longer than a tile, else 0)
+ * and end in out_dev.  out_dev may be keys_dev itself; work_dev may overlap neither.
+ *
+ * jamun_swd_merge: sorted a_dev [n_proj] rows of n keys, a_stride (>= n) floats apart, and b_dev [n_proj] rows of m keys likewise ->
+ * out_dev fp32 [n_proj][n + m], sorted; n + m fits 31 bits.  The device code is that of the sort's merge pass.
+ *
+ * jamun_swd_w2sq: sorted u_dev (rows of n) and v_dev (rows of m) as above -> out_dev fp64 [n_proj], the integral over q in [0, 1] of
+ * (F^-1(q) - G^-1(q))^2 for the two empirical quantile functions: on the grid of n m cells the overlaps of u's cell i (length m) and v's
+ * cell j (length n) contribute  w * (double(u_i) - double(v_j))^2,  w the overlap's integer length, formed as a difference, a square and a
+ * product, each rounded once; the sum is divided by double(n m).  The terms are added in a fixed order (work_dev: jamun_swd_w2sq_work
+ * doubles), so the same inputs give the same bits in every run, within (n + m) 2^-52 relative of any other order.  A non-finite key makes
+ * its own column's value non-finite and touches no other column.
+ *
+ * A count below 1, width or n_proj outside its range, cuts that do not ascend strictly within [1, n_frames], a row stride below the
+ * row's length, n + m above 2^31 - 1, a capacity (in floats, or in doubles for jamun_swd_w2sq) below the need or a NULL pointer that is
+ * needed is JAMUN_ERR_INVALID and nothing is written.  Caller-owned buffers, work queued on `stream`, no synchronisation, no allocation,
+ * nothing read back. */
+int jamun_swd_project(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, const float* proj_dev, int32_t n_proj, float* out_dev,
+                      int64_t out_capacity, void* stream);
+int jamun_swd_sort_work(int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts, int64_t* n_floats);
+int jamun_swd_sort_segments(const float* keys_dev, int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts, float* out_dev,
+                            int64_t out_capacity, float* work_dev, int64_t work_capacity, void* stream);
+int jamun_swd_merge(const float* a_dev, int64_t a_stride, int32_t n, const float* b_dev, int64_t b_stride, int32_t m, int32_t n_proj, float* out_dev,
+                    int64_t out_capacity, void* stream);
+int jamun_swd_w2sq_work(int32_t n, int32_t m, int32_t n_proj, int64_t* n_doubles);
+int jamun_swd_w2sq(const float* u_dev, int64_t u_stride, int32_t n, const float* v_dev, int64_t v_stride, int32_t m, int32_t n_proj, double* out_dev,
+                   double* work_dev, int64_t work_capacity, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

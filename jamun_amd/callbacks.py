@@ -575,6 +575,21 @@ class MSMMetricsCallback(TrajectoryMetricCallback):
         super().__init__(datasets, functools.partial(MSMMetrics, **kw))
 
 
+class SlicedWassersteinMetricsCallback(TrajectoryMetricCallback):
+    """`TrajectoryMetricCallback` over `swd.SlicedWassersteinMetrics` (the second curve of the reference's ``RamachandranPlotMetrics``:
+    ``compute_sliced_Wasserstein_distance_vs_num_samples``, without the ``ot`` package): per chain and for the joined trajectory the
+    sliced Wasserstein distance of the (cos, sin) descriptors of phi and psi from the true trajectory's against the number of samples,
+    under ``<output_dir>/<label>/sliced_wasserstein/``.  Keyword arguments go to the meter (``n_projections``, ``seed``, ``pairing``,
+    ``reference``, ``output_dir``, ``sample_key``, ``device``)."""
+
+    def __init__(self, datasets: Sequence, **kw):
+        import functools
+
+        from .swd import SlicedWassersteinMetrics
+
+        super().__init__(datasets, functools.partial(SlicedWassersteinMetrics, **kw))
+
+
 class MeasureSamplingTimeCallback:
     """Wall time per batch and per sampled conformation (one saved (walker, frame) pair — the reference's unit,
     ``callbacks/sampler/_measure_sampling_time.py:57,71``).  Writes ``sampler/timing.json`` on rank 0."""

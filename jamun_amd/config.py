@@ -39,6 +39,7 @@ TARGET_ALIASES = {
     "jamun.callbacks.sampler.ChemicalValidityMetricsCallback": "jamun_amd.callbacks.ChemicalValidityMetricsCallback",
     "jamun.callbacks.sampler.TICAMetricsCallback": "jamun_amd.callbacks.TICAMetricsCallback",
     "jamun.callbacks.sampler.MSMMetricsCallback": "jamun_amd.callbacks.MSMMetricsCallback",
+    "jamun.callbacks.sampler.SlicedWassersteinMetricsCallback": "jamun_amd.callbacks.SlicedWassersteinMetricsCallback",
     "jamun.sampling.walkjump.MeasurementDependentParametersCallback": "jamun_amd.sampling.MeasurementDependentParametersCallback",
     "jamun.sampling.walkjump.InterpolateParametersCallback": "jamun_amd.sampling.InterpolateParametersCallback",
     "jamun.utils.ModelSamplingWrapper": "jamun_amd.sampling.ModelSamplingWrapper",

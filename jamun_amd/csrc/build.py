@@ -20,7 +20,7 @@ ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libjamun_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 SOURCES = ["jamun_kernels.hip", "jamun_conv.hip", "jamun_conv_initv.hip", "jamun_conv_dg.hip", "jamun_tprod.hip", "jamun_conv_mf.hip", "jamun_conv_tail.hip", "jamun_conv_ml.hip",
-           "jamun_node.hip", "jamun_sepconv.hip", "jamun_wide.hip", "jamun_traj.hip", "jamun_superpose.hip", "jamun_intcoord.hip", "jamun_hist.hip", "jamun_validity.hip", "jamun_tica.hip", "jamun_msm.hip", "jamun_api.cpp", "jamun_frames.cpp", "jamun_pack.cpp", "jamun_plan.cpp"]
+           "jamun_node.hip", "jamun_sepconv.hip", "jamun_wide.hip", "jamun_traj.hip", "jamun_superpose.hip", "jamun_intcoord.hip", "jamun_hist.hip", "jamun_validity.hip", "jamun_tica.hip", "jamun_msm.hip", "jamun_swd.hip", "jamun_api.cpp", "jamun_frames.cpp", "jamun_pack.cpp", "jamun_plan.cpp"]
 HEADERS = ["jamun_internal.h", "jamun_host.h", "jamun_conv_form.h", "jamun_conv_mf_layout.h", "jamun_dev.h", "jamun_split.h", os.path.join(ROOT, "include", "jamun_hip.h")]
 DEPS = SOURCES + HEADERS
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

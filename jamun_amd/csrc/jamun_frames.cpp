@@ -2,7 +2,8 @@
 // (jamun_traj.hip), superposition (jamun_superpose.hip), internal coordinates (jamun_intcoord.hip), histograms of angle pairs with their
 // Jensen-Shannon divergence (jamun_hist.hip), chemical validity (jamun_validity.hip), the reductions behind TICA: lagged moments,
 // projection, autocovariance sums (jamun_tica.hip), and those behind k-means and the Markov state model: nearest centres, cluster sums,
-// transition and occupancy counts (jamun_msm.hip).  Every refusal is raised before any HIP call.
+// transition and occupancy counts (jamun_msm.hip), and the sliced Wasserstein distance: projection, segment sort, merge, quantile integral
+// (jamun_swd.hip).  Every refusal is raised before any HIP call.
 // The order of an entry's checks decides which message a caller with two faults sees, and the entries differ in it on purpose: where a
 // shared check below would change an order or a text, the entry keeps a line of its own.  Every entry's checks read top to bottom.
 #include "jamun_host.h"
@@ -70,7 +71,33 @@ int32_t check_states(int32_t n_states, const int32_t* map_dev, int32_t n_in) {
   return map_dev ? n_in : n_states;
 }
 
-constexpr int64_t kMaxModel = 1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
+// the cuts of jamun_swd_sort_segments (and the two counts they are checked against) as the kernels take them
+JamunHistCuts swd_cuts(int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts) {
+  check_range("n_frames", n_frames, 1, INT32_MAX);
+  check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
+  check_n_cuts(n_cuts);
+  if (!cuts) throw Err(JAMUN_ERR_INVALID, "null argument");
+  JamunHistCuts k;
+  k.n = n_cuts;
+  for (int c = 0; c < JAMUN_HIST_MAX_CUTS; ++c) k.cut[c] = c < n_cuts ? cuts[c] : 0;
+  for (int c = 0; c < n_cuts; ++c)
+    if (k.cut[c] < 1 || k.cut[c] > n_frames || (c > 0 && k.cut[c] <= k.cut[c - 1]))
+      throw Err(JAMUN_ERR_INVALID, "cuts[" + std::to_string(c) + "] = " + std::to_string(k.cut[c]) + ": the cuts must ascend strictly within [1, " +
+                                       std::to_string(n_frames) + "]");
+  return k;
+}
+
+// two sets of n_proj sorted columns of n and m keys, their rows a_stride and b_stride floats apart
+void swd_columns(int64_t a_stride, int32_t n, int64_t b_stride, int32_t m, int32_t n_proj) {
+  check_range("n", n, 1, INT32_MAX);
+  check_range("m", m, 1, INT32_MAX);
+  check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
+  if (a_stride < n || b_stride < m)
+    throw Err(JAMUN_ERR_INVALID, "row strides " + std::to_string(a_stride) + " and " + std::to_string(b_stride) + " are below the lengths " +
+                                     std::to_string(n) + " and " + std::to_string(m));
+}
+
+constexpr int64_t kMaxModel =1000000000000000ll;  // model numbers stay below 10^15 (16 digits: the MODEL line fits the kernel's header budget)
 
 int64_t checked_pdb_nbytes(int64_t body_len, int64_t first_model, int64_t n_frames) {
   if (body_len < 0 || first_model < 0 || n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
@@ -363,6 +390,75 @@ int jamun_label_counts(const int32_t* labels_dev, int32_t n_frames, const int32_
     if (n_frames == 0) return;  // (nothing to count)
     if (!labels_dev || !bounds_dev || !counts_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
     launch_label_counts(labels_dev, n_frames, map_dev, n_labels, n_states, bounds_dev, n_seg, (long long*)counts_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+// ---- sliced Wasserstein distance: projection, segment sort, merge, quantile integral (jamun_swd.hip) -----------------------------------------
+
+int jamun_swd_project(const float* x_dev, int64_t row_stride, int32_t n_frames, int32_t width, const float* proj_dev, int32_t n_proj, float* out_dev,
+                      int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    check_range("n_frames", n_frames, 1, INT32_MAX);
+    check_range("width", width, 1, JAMUN_SWD_MAX_WIDTH);
+    check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
+    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    require_capacity("out_capacity", out_capacity, (int64_t)n_frames * n_proj, "keys", "floats");
+    if (!x_dev || !proj_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_swd_project(x_dev, row_stride, n_frames, width, proj_dev, n_proj, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_swd_sort_work(int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts, int64_t* n_floats) {
+  return guarded([&] {
+    if (!n_floats) throw Err(JAMUN_ERR_INVALID, "null argument");
+    *n_floats = swd_sort_work_floats(n_frames, n_proj, swd_cuts(n_frames, n_proj, cuts, n_cuts));
+  });
+}
+
+int jamun_swd_sort_segments(const float* keys_dev, int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts, float* out_dev,
+                            int64_t out_capacity, float* work_dev, int64_t work_capacity, void* stream) {
+  return guarded([&] {
+    const JamunHistCuts k = swd_cuts(n_frames, n_proj, cuts, n_cuts);
+    require_capacity("out_capacity", out_capacity, (int64_t)n_frames * n_proj, "keys", "floats");
+    const int64_t need = swd_sort_work_floats(n_frames, n_proj, k);
+    require_capacity("work_capacity", work_capacity, need, "merge passes", "floats");
+    if (!keys_dev || !out_dev || (need > 0 && !work_dev)) throw Err(JAMUN_ERR_INVALID, "null argument");
+    if (need > 0 && work_dev < out_dev + (int64_t)n_frames * n_proj && out_dev < work_dev + need)
+      throw Err(JAMUN_ERR_INVALID, "work_dev overlaps out_dev");
+    HIPCHECK(launch_swd_sort_segments(keys_dev, n_frames, n_proj, k, out_dev, work_dev, (hipStream_t)stream));
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_swd_merge(const float* a_dev, int64_t a_stride, int32_t n, const float* b_dev, int64_t b_stride, int32_t m, int32_t n_proj, float* out_dev,
+                    int64_t out_capacity, void* stream) {
+  return guarded([&] {
+    swd_columns(a_stride, n, b_stride, m, n_proj);
+    if ((int64_t)n + m > INT32_MAX) throw Err(JAMUN_ERR_INVALID, "n + m = " + std::to_string((int64_t)n + m) + " does not fit 31 bits");
+    require_capacity("out_capacity", out_capacity, ((int64_t)n + m) * n_proj, "merged columns", "floats");
+    if (!a_dev || !b_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_swd_merge(a_dev, a_stride, n, b_dev, b_stride, m, n_proj, out_dev, (hipStream_t)stream);
+    HIPCHECK(hipGetLastError());
+  });
+}
+
+int jamun_swd_w2sq_work(int32_t n, int32_t m, int32_t n_proj, int64_t* n_doubles) {
+  return guarded([&] {
+    if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
+    swd_columns(n, n, m, m, n_proj);
+    *n_doubles = swd_w2sq_work_doubles(n, m, n_proj);
+  });
+}
+
+int jamun_swd_w2sq(const float* u_dev, int64_t u_stride, int32_t n, const float* v_dev, int64_t v_stride, int32_t m, int32_t n_proj, double* out_dev,
+                   double* work_dev, int64_t work_capacity, void* stream) {
+  return guarded([&] {
+    swd_columns(u_stride, n, v_stride, m, n_proj);
+    require_capacity("work_capacity", work_capacity, swd_w2sq_work_doubles(n, m, n_proj), "partial sums", "doubles");
+    if (!u_dev || !v_dev || !out_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
+    launch_swd_w2sq(u_dev, u_stride, n, v_dev, v_stride, m, n_proj, out_dev, work_dev, (hipStream_t)stream);
     HIPCHECK(hipGetLastError());
   });
 }

@@ -561,3 +561,15 @@ void launch_cluster_sums(const double* y, long long row_stride, int n_frames, in
 void launch_transition_counts(const int* labels, int n_frames, int lag, const int* map, int n_in, int n_states, long long* counts, hipStream_t st);  // (lag < n_frames)
 void launch_label_counts(const int* labels, int n_frames, const int* map, int n_in, int n_states, const int* bounds, int n_seg, long long* counts,
                          hipStream_t st);
+// jamun_swd.hip — sliced Wasserstein distance: projection of descriptor rows on directions, sort of the projected columns over segments of
+// frames (by the order image of jamun_amd/swd.py), merge of sorted columns, quantile integral of two sorted columns; every count >= 1
+#define JAMUN_SWD_TILE 4096       // keys a workgroup sorts in LDS: the unit of the merge passes (native.SWD_TILE mirrors it for the tests)
+#define JAMUN_SWD_MAX_WIDTH 128   // descriptor columns the projection takes (native.SWD_MAX_WIDTH)
+#define JAMUN_SWD_MAX_PROJ 64     // directions (native.SWD_MAX_PROJ)
+long long swd_sort_work_floats(int n_frames, int n_proj, const JamunHistCuts& cuts);
+long long swd_w2sq_work_doubles(int n, int m, int n_proj);
+void launch_swd_project(const float* x, long long row_stride, int n_frames, int width, const float* proj, int n_proj, float* out, hipStream_t st);
+hipError_t launch_swd_sort_segments(const float* keys, int n_frames, int n_proj, const JamunHistCuts& cuts, float* out, float* work, hipStream_t st);
+void launch_swd_merge(const float* a, long long a_stride, int n, const float* b, long long b_stride, int m, int n_proj, float* out, hipStream_t st);
+void launch_swd_w2sq(const float* u, long long u_stride, int n, const float* v, long long v_stride, int m, int n_proj, double* out, double* work,
+                     hipStream_t st);

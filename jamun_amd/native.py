@@ -1170,3 +1170,127 @@ def label_counts(labels: torch.Tensor, bounds, n_states: int, state_map=None, ou
     with torch.cuda.device(dev):
         _lib.check(lib.jamun_label_counts(_ptr(labels), T, _ptr(state_map), n_in, n_states, _ptr(bounds), n_seg, _ptr(out), _stream()))
     return out
+
+
+# ---- sliced Wasserstein distance: projection, segment sort, merge, quantile integral (jamun_swd.hip) ---------------------------------------
+
+SWD_TILE = 4096      # keys a workgroup sorts in LDS, the unit of the merge passes (JAMUN_SWD_TILE, jamun_internal.h)
+SWD_MAX_WIDTH = 128  # descriptor columns `swd_project` takes (JAMUN_SWD_MAX_WIDTH)
+SWD_MAX_PROJ = 64    # directions (JAMUN_SWD_MAX_PROJ)
+
+
+def check_swd_shapes(width: int, n_proj: int) -> None:
+    """The limits of the device path on the descriptor columns and the directions (``ValueError`` otherwise), before anything needs a GPU."""
+    if not (1 <= width <= SWD_MAX_WIDTH and 1 <= n_proj <= SWD_MAX_PROJ):
+        raise ValueError(f"{width} descriptor columns on {n_proj} directions: the device path takes 1 to {SWD_MAX_WIDTH} columns and 1 to "
+                         f"{SWD_MAX_PROJ} directions (the host functions of jamun_amd.swd have no limit)")
+
+
+def _swd_columns(name: str, a) -> Tuple[int, int]:
+    """The shape rule of a set of key columns ``[L, n]``, before anything needs a GPU: ``1 <= L <= 64``, ``n >= 1``.  Returns ``(L, n)``."""
+    if not torch.is_tensor(a) or a.ndim != 2 or a.shape[1] < 1 or not 1 <= a.shape[0] <= SWD_MAX_PROJ:
+        raise ValueError(f"{name} must be a [directions, keys] tensor of 1 to {SWD_MAX_PROJ} directions and at least one key, got "
+                         f"{tuple(getattr(a, 'shape', ()))}")
+    return int(a.shape[0]), int(a.shape[1])
+
+
+def _swd_rows(name: str, a: torch.Tensor, L: int, n: int, device=None) -> int:
+    """``RuntimeError`` unless ``a`` is float32 on a GPU (``device`` if given) with adjacent keys; returns the row stride in floats."""
+    if (not a.is_cuda or a.dtype != torch.float32 or (n > 1 and a.stride(1) != 1) or (L > 1 and a.stride(0) < n)
+            or (device is not None and a.device != device)):
+        raise RuntimeError(f"{name} must be a float32 tensor on the GPU{'' if device is None else f' ({device})'} with adjacent keys, got {a.dtype} "
+                           f"{tuple(a.shape)} strides {tuple(a.stride())} on {a.device}")
+    _fit_31_bits(f"{n} keys: the count must fit 31 bits", n)
+    return int(a.stride(0)) if L > 1 else n
+
+
+def swd_project(x: torch.Tensor, proj, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the projection of the descriptor rows ``x [T, W]`` (device fp32 with adjacent columns: what `internal_coords` returns with
+    ``cossin``, or a view of it with a row stride) on the directions ``proj [W, L]`` (float32; a host array is uploaded, a tensor on the
+    device is used as it is) on the current stream: float32 ``[L, T]``, bit for bit `swd.project_host`.  ``T >= 1``, ``1 <= W <= 128``,
+    ``1 <= L <= 64`` (``ValueError`` otherwise, before anything needs a GPU).  ``out`` (contiguous float32 of that shape on the device)
+    receives the result; default a new tensor.  See ``jamun_swd_project``."""
+    if not torch.is_tensor(x) or x.ndim != 2 or x.shape[0] < 1:
+        raise ValueError(f"x must be a [frames, width] tensor of at least one frame, got {tuple(getattr(x, 'shape', ()))}")
+    T, W = int(x.shape[0]), int(x.shape[1])
+    shape_p = tuple(getattr(proj, "shape", ()))
+    if len(shape_p) != 2 or shape_p[0] != W:
+        raise ValueError(f"proj must have shape [{W}, L], got {shape_p}")
+    L = int(shape_p[1])
+    check_swd_shapes(W, L)
+    if not torch.is_tensor(proj):
+        proj = torch.from_numpy(np.ascontiguousarray(proj))
+    if proj.dtype != torch.float32:
+        raise ValueError(f"proj must hold float32, got {proj.dtype}")
+    row_stride = _feature_rows(x, T, W)
+    lib = _lib.load()
+    dev = x.device
+    proj = proj.to(dev).contiguous()
+    out = _result("out", out, (L, T), torch.float32, dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.jamun_swd_project(_ptr(x), row_stride, T, W, _ptr(proj), L, _ptr(out), int(out.numel()), _stream()))
+    return out
+
+
+def swd_sort_segments(keys: torch.Tensor, cuts, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the sort of every segment of every column of ``keys [L, T]`` (contiguous device fp32: what `swd_project` returns) on the
+    current stream: float32 ``[L, T]`` whose frames ``cuts[c-1] <= t < cuts[c]`` are sorted by `swd.order_image`, each segment on its
+    own; frames from the last cut on are copied.  ``cuts`` as `check_cuts` takes them (a host array).  Out of place; ``out`` (contiguous
+    float32 of that shape on the device) receives the result and may be ``keys`` itself; default a new tensor.  The workspace of the merge
+    passes is this module's.  `swd.sort_segments_host` is the specification: the bits are its bits.  See ``jamun_swd_sort_segments``."""
+    L, T = _swd_columns("keys", keys)
+    cuts = np.ascontiguousarray(check_cuts(cuts, T), dtype=np.int32)
+    if _swd_rows("keys", keys, L, T) != T:
+        raise RuntimeError(f"keys must be contiguous, got strides {tuple(keys.stride())}")
+    lib = _lib.load()
+    dev = keys.device
+    out = _result("out", out, (L, T), torch.float32, dev)
+    need = C.c_int64()
+    _lib.check(lib.jamun_swd_sort_work(T, L, cuts.ctypes.data, int(cuts.shape[0]), C.byref(need)))
+    with torch.cuda.device(dev):
+        work = _tica_workspace(dev, (need.value + 1) // 2).view(torch.float32)
+        _lib.check(lib.jamun_swd_sort_segments(_ptr(keys), T, L, cuts.ctypes.data, int(cuts.shape[0]), _ptr(out), int(out.numel()), _ptr(work),
+                                               int(work.numel()), _stream()))
+    return out
+
+
+def swd_merge(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the merge of the sorted columns ``a [L, n]`` and ``b [L, m]`` (device fp32 with adjacent keys; a row stride is taken, so a
+    segment of `swd_sort_segments`' result is read in place) on the current stream: float32 ``[L, n + m]``, sorted by `swd.order_image`.
+    ``out`` (contiguous float32 of that shape on the device, apart from both) receives the result; default a new tensor.
+    `swd.merge_sorted_host` is the specification.  See ``jamun_swd_merge``."""
+    L, n = _swd_columns("a", a)
+    Lb, m = _swd_columns("b", b)
+    if Lb != L:
+        raise ValueError(f"a and b must have the same number of directions, got {L} and {Lb}")
+    if n + m > 0x7FFFFFFF:
+        raise ValueError(f"{n} + {m} keys: the sum must fit 31 bits")
+    sa = _swd_rows("a", a, L, n)
+    sb = _swd_rows("b", b, L, m, a.device)
+    lib = _lib.load()
+    out = _result("out", out, (L, n + m), torch.float32, a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.jamun_swd_merge(_ptr(a), sa, n, _ptr(b), sb, m, L, _ptr(out), int(out.numel()), _stream()))
+    return out
+
+
+def swd_w2sq(u: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Queue the squared 2-Wasserstein distances of the sorted columns ``u [L, n]`` and ``v [L, m]`` (as `swd_merge` takes them) on the
+    current stream: float64 ``[L]``, the quantile integral of `swd.w2sq_sorted_host` with every term formed as there and added in a
+    fixed order: the same bits in every run, within ``(n + m) 2^-52`` relative of the specification.  ``out`` (contiguous float64 ``[L]`` on
+    the device) receives the result; default a new tensor.  The workspace is this module's.  See ``jamun_swd_w2sq``."""
+    L, n = _swd_columns("u", u)
+    Lv, m = _swd_columns("v", v)
+    if Lv != L:
+        raise ValueError(f"u and v must have the same number of directions, got {L} and {Lv}")
+    su = _swd_rows("u", u, L, n)
+    sv = _swd_rows("v", v, L, m, u.device)
+    lib = _lib.load()
+    dev = u.device
+    out = _result("out", out, (L,), torch.float64, dev)
+    need = C.c_int64()
+    _lib.check(lib.jamun_swd_w2sq_work(n, m, L, C.byref(need)))
+    with torch.cuda.device(dev):
+        work = _tica_workspace(dev, need.value)
+        _lib.check(lib.jamun_swd_w2sq(_ptr(u), su, n, _ptr(v), sv, m, L, _ptr(out), _ptr(work), int(work.numel()), _stream()))
+    return out

@@ -12,8 +12,8 @@ trajectory.  This module is that curve without mdtraj, scipy or matplotlib:
 A histogram over frames ``[0, k)`` for several k is kept as SEGMENT histograms (frames ``cuts[c-1] <= t < cuts[c]``); the histogram of a
 prefix is the integer sum of its segments, so nothing is counted twice and a joined trajectory is summed from its chains' counts.
 
-Out of scope: the plots, the animations and the wandb tables of the reference's ``RamachandranPlotMetrics``, and its sliced Wasserstein
-distance (it needs the ``ot`` package).  Under several ranks each rank meters the walkers it owns and rank 0 writes its own; the chains
+Out of scope: the plots, the animations and the wandb tables of the reference's ``RamachandranPlotMetrics``.  Its second curve, the
+sliced Wasserstein distance, is `swd.SlicedWassersteinMetrics` (a meter of its own: this one is unchanged).  Under several ranks each rank meters the walkers it owns and rank 0 writes its own; the chains
 are not gathered.
 """
 
@@ -168,7 +168,7 @@ class RamachandranMetrics(TrajectoryMeter):
     ``internal_coords_host(...).astype(float32)``.  ``"host"`` forces the host path, ``"device"`` makes a missing device path an error.
     `compute` returns ``{"<label>/js_divergence/pred_traj_joined": the joined trajectory's last pooled value}``.
 
-    Out of scope: plots, animations, wandb and the sliced Wasserstein distance of the reference's class."""
+    Out of scope: plots, animations and wandb; the sliced Wasserstein distance of the reference's class is `swd.SlicedWassersteinMetrics`."""
 
     DIRECTORY = "ramachandran"
 
