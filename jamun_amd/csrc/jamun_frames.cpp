@@ -6,6 +6,9 @@
 // (jamun_swd.hip).  Every refusal is raised before any HIP call.
 // The order of an entry's checks decides which message a caller with two faults sees, and the entries differ in it on purpose: where a
 // shared check below would change an order or a text, the entry keeps a line of its own.  Every entry's checks read top to bottom.
+// The shared checks: check_range (every "NAME V is outside [LO, HI]"), check_row_stride, require_capacity, parse_cuts (the cuts of the
+// histograms and of the segment sort), check_tica_lag, check_centers, check_states, swd_columns.  tests/golden/frames_refusals.json pins
+// the code and the text of every refusal that ends before a launch, and which of two faults is the one reported.
 #include "jamun_host.h"
 
 namespace {
@@ -27,34 +30,19 @@ void require_capacity(const char* name, int64_t have, int64_t need, const char* 
     throw Err(JAMUN_ERR_INVALID, std::string(name) + " " + std::to_string(have) + " is too small: the " + what + " need " + std::to_string(need) + " " + unit);
 }
 
-void check_bins(int32_t bins) {
-  if (bins < 1 || bins > JAMUN_HIST_MAX_BINS)
-    throw Err(JAMUN_ERR_INVALID, "bins " + std::to_string(bins) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_BINS) + "]");
+void check_range(const char* name, int64_t v, int64_t lo, int64_t hi) {
+  if (v < lo || v > hi)
+    throw Err(JAMUN_ERR_INVALID, std::string(name) + " " + std::to_string(v) + " is outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
 }
 
-void check_n_cuts(int32_t n_cuts) {
-  if (n_cuts < 1 || n_cuts > JAMUN_HIST_MAX_CUTS)
-    throw Err(JAMUN_ERR_INVALID, "n_cuts " + std::to_string(n_cuts) + " is outside [1, " + std::to_string(JAMUN_HIST_MAX_CUTS) + "]");
-}
-
-void check_tica_width(int32_t width) {
-  if (width < 1 || width > JAMUN_TICA_MAX_WIDTH)
-    throw Err(JAMUN_ERR_INVALID, "width " + std::to_string(width) + " is outside [1, " + std::to_string(JAMUN_TICA_MAX_WIDTH) + "]");
+// rows `stride` elements apart hold `width` adjacent ones; `what` words the width: "the width " or "d = "
+void check_row_stride(int64_t stride, int32_t width, const char* what) {
+  if (stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(stride) + " is below " + what + std::to_string(width));
 }
 
 void check_tica_lag(int32_t lag, int32_t n_frames) {
   if (lag < 1 || lag >= n_frames)
     throw Err(JAMUN_ERR_INVALID, "lag " + std::to_string(lag) + " is outside [1, n_frames = " + std::to_string(n_frames) + ")");
-}
-
-void check_tica_acf_lag(int32_t max_lag) {
-  if (max_lag < 0 || max_lag > JAMUN_TICA_MAX_ACF_LAG)
-    throw Err(JAMUN_ERR_INVALID, "max_lag " + std::to_string(max_lag) + " is outside [0, " + std::to_string(JAMUN_TICA_MAX_ACF_LAG) + "]");
-}
-
-void check_range(const char* name, int64_t v, int64_t lo, int64_t hi) {
-  if (v < lo || v > hi)
-    throw Err(JAMUN_ERR_INVALID, std::string(name) + " " + std::to_string(v) + " is outside [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
 }
 
 void check_centers(int32_t k, int32_t d) {
@@ -71,11 +59,9 @@ int32_t check_states(int32_t n_states, const int32_t* map_dev, int32_t n_in) {
   return map_dev ? n_in : n_states;
 }
 
-// the cuts of jamun_swd_sort_segments (and the two counts they are checked against) as the kernels take them
-JamunHistCuts swd_cuts(int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts) {
-  check_range("n_frames", n_frames, 1, INT32_MAX);
-  check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
-  check_n_cuts(n_cuts);
+// n_cuts cuts (a host array) ascending strictly within [1, n_frames], as the kernels take them: their number, the pointer, the ascent
+JamunHistCuts parse_cuts(const int32_t* cuts, int32_t n_cuts, int32_t n_frames) {
+  check_range("n_cuts", n_cuts, 1, JAMUN_HIST_MAX_CUTS);
   if (!cuts) throw Err(JAMUN_ERR_INVALID, "null argument");
   JamunHistCuts k;
   k.n = n_cuts;
@@ -85,6 +71,13 @@ JamunHistCuts swd_cuts(int32_t n_frames, int32_t n_proj, const int32_t* cuts, in
       throw Err(JAMUN_ERR_INVALID, "cuts[" + std::to_string(c) + "] = " + std::to_string(k.cut[c]) + ": the cuts must ascend strictly within [1, " +
                                        std::to_string(n_frames) + "]");
   return k;
+}
+
+// the cuts of jamun_swd_sort_segments, behind the two counts they are checked against
+JamunHistCuts swd_cuts(int32_t n_frames, int32_t n_proj, const int32_t* cuts, int32_t n_cuts) {
+  check_range("n_frames", n_frames, 1, INT32_MAX);
+  check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
+  return parse_cuts(cuts, n_cuts, n_frames);
 }
 
 // two sets of n_proj sorted columns of n and m keys, their rows a_stride and b_stride floats apart
@@ -197,17 +190,9 @@ int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_fr
                        int64_t counts_capacity, uint32_t* skipped_dev, void* stream) {
   return guarded([&] {
     if (row_stride < 0 || n_frames < 0 || width < 0 || n_pairs < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_bins(bins);
-    check_n_cuts(n_cuts);
-    if (!cuts) throw Err(JAMUN_ERR_INVALID, "null argument");
-    JamunHistCuts k;
-    k.n = n_cuts;
-    for (int c = 0; c < JAMUN_HIST_MAX_CUTS; ++c) k.cut[c] = c < n_cuts ? cuts[c] : 0;
-    for (int c = 0; c < n_cuts; ++c)
-      if (k.cut[c] < 1 || k.cut[c] > n_frames || (c > 0 && k.cut[c] <= k.cut[c - 1]))
-        throw Err(JAMUN_ERR_INVALID, "cuts[" + std::to_string(c) + "] = " + std::to_string(k.cut[c]) + ": the cuts must ascend strictly within [1, " +
-                                         std::to_string(n_frames) + "]");
-    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    check_range("bins", bins, 1, JAMUN_HIST_MAX_BINS);
+    const JamunHistCuts k = parse_cuts(cuts, n_cuts, n_frames);
+    check_row_stride(row_stride, width, "the width ");
     if (n_pairs > 65535) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is above 65535");
     const int64_t need = (int64_t)n_cuts * (int64_t)n_pairs * bins * bins;  // (< 2^37)
     require_capacity("counts_capacity", counts_capacity, need, "histograms", "counters");
@@ -224,9 +209,9 @@ int jamun_hist2d_pairs(const float* angles_dev, int64_t row_stride, int32_t n_fr
 int jamun_js_divergence(const uint32_t* counts_dev, int32_t n_cuts, int32_t n_pairs, int32_t bins, const uint32_t* ref_dev, int32_t n_ref_pairs,
                         double* pooled_dev, double* per_pair_dev, void* stream) {
   return guarded([&] {
-    check_bins(bins);
-    check_n_cuts(n_cuts);
-    if (n_pairs < 1 || n_pairs > 65534) throw Err(JAMUN_ERR_INVALID, "n_pairs " + std::to_string(n_pairs) + " is outside [1, 65534]");
+    check_range("bins", bins, 1, JAMUN_HIST_MAX_BINS);
+    check_range("n_cuts", n_cuts, 1, JAMUN_HIST_MAX_CUTS);
+    check_range("n_pairs", n_pairs, 1, 65534);
     if (n_ref_pairs != 1 && n_ref_pairs != n_pairs)
       throw Err(JAMUN_ERR_INVALID, "n_ref_pairs " + std::to_string(n_ref_pairs) + " is neither 1 nor n_pairs = " + std::to_string(n_pairs));
     if (!counts_dev || !ref_dev || !pooled_dev || !per_pair_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
@@ -243,8 +228,7 @@ int jamun_validity_counts(const float* xyz_dev, int64_t frame_stride, int64_t at
   return guarded([&] {
     // (not FramesView::negative: a negative n_atoms is answered with its range below)
     if (frame_stride < 0 || atom_stride < 0 || n_frames < 0 || n_bonds < 0 || counts_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    if (n_atoms < 1 || n_atoms > JAMUN_VALIDITY_MAX_ATOMS)
-      throw Err(JAMUN_ERR_INVALID, "n_atoms " + std::to_string(n_atoms) + " is outside [1, " + std::to_string(JAMUN_VALIDITY_MAX_ATOMS) + "]");
+    check_range("n_atoms", n_atoms, 1, JAMUN_VALIDITY_MAX_ATOMS);
     const int64_t need = 2 * (int64_t)n_frames;
     require_capacity("counts_capacity", counts_capacity, need, "frames", "counters");
     if (n_frames == 0) return;  // (nothing to write)
@@ -264,7 +248,7 @@ int jamun_lagged_moments_work(int32_t n_frames, int32_t width, int32_t lag, int6
   return guarded([&] {
     if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
     if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_tica_width(width);
+    check_range("width", width, 1, JAMUN_TICA_MAX_WIDTH);
     if (n_frames == 0) {
       *n_doubles = 0;
       return;
@@ -278,10 +262,10 @@ int jamun_lagged_moments(const float* x_dev, int64_t row_stride, int32_t n_frame
                          double* work_dev, int64_t work_capacity, void* stream) {
   return guarded([&] {
     if (row_stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_tica_width(width);
+    check_range("width", width, 1, JAMUN_TICA_MAX_WIDTH);
     if (n_frames == 0) return;  // (nothing to write)
     check_tica_lag(lag, n_frames);
-    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    check_row_stride(row_stride, width, "the width ");
     require_capacity("work_capacity", work_capacity, moments_work_doubles(n_frames, width, lag), "partial sums", "doubles");
     if (!x_dev || !sums_dev || !moments_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
     launch_lagged_moments(x_dev, row_stride, n_frames, width, lag, sums_dev, moments_dev, work_dev, (hipStream_t)stream);
@@ -293,9 +277,9 @@ int jamun_project_frames(const float* x_dev, int64_t row_stride, int32_t n_frame
                          double* out_dev, int64_t out_capacity, void* stream) {
   return guarded([&] {
     if (row_stride < 0 || n_frames < 0 || out_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_tica_width(width);
+    check_range("width", width, 1, JAMUN_TICA_MAX_WIDTH);
     if (d < 1 || d > width) throw Err(JAMUN_ERR_INVALID, "d " + std::to_string(d) + " is outside [1, width = " + std::to_string(width) + "]");
-    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    check_row_stride(row_stride, width, "the width ");
     require_capacity("out_capacity", out_capacity, (int64_t)n_frames * d, "projections", "doubles");
     if (n_frames == 0) return;  // (nothing to write)
     if (!x_dev || !mean_dev || !v_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
@@ -308,7 +292,7 @@ int jamun_autocov_sums_work(int32_t n_frames, int32_t max_lag, int64_t* n_double
   return guarded([&] {
     if (!n_doubles) throw Err(JAMUN_ERR_INVALID, "null argument");
     if (n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_tica_acf_lag(max_lag);
+    check_range("max_lag", max_lag, 0, JAMUN_TICA_MAX_ACF_LAG);
     *n_doubles = n_frames == 0 ? 0 : autocov_work_doubles(n_frames, max_lag);
   });
 }
@@ -317,7 +301,7 @@ int jamun_autocov_sums(const double* y_dev, int64_t stride, int32_t n_frames, in
                        void* stream) {
   return guarded([&] {
     if (stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
-    check_tica_acf_lag(max_lag);
+    check_range("max_lag", max_lag, 0, JAMUN_TICA_MAX_ACF_LAG);
     if (n_frames == 0) return;  // (nothing to write)
     if (stride < 1) throw Err(JAMUN_ERR_INVALID, "stride 0: the values of y must lie apart");
     require_capacity("work_capacity", work_capacity, autocov_work_doubles(n_frames, max_lag), "partial sums", "doubles");
@@ -334,7 +318,7 @@ int jamun_assign_centers(const double* y_dev, int64_t row_stride, int32_t n_fram
   return guarded([&] {
     if (row_stride < 0 || n_frames < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
     check_centers(k, d);
-    if (row_stride < d) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below d = " + std::to_string(d));
+    check_row_stride(row_stride, d, "d = ");
     if ((prev_labels_dev == nullptr) != (n_changed_dev == nullptr))
       throw Err(JAMUN_ERR_INVALID, "prev_labels_dev and n_changed_dev go together: one of them is null");
     if (n_frames == 0) return;  // (nothing to write)
@@ -359,7 +343,7 @@ int jamun_cluster_sums(const double* y_dev, int64_t row_stride, int32_t n_frames
   return guarded([&] {
     if (row_stride < 0 || n_frames < 0 || work_capacity < 0) throw Err(JAMUN_ERR_INVALID, "negative argument");
     check_centers(k, d);
-    if (row_stride < d) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below d = " + std::to_string(d));
+    check_row_stride(row_stride, d, "d = ");
     if (n_frames == 0) return;  // (nothing to write)
     require_capacity("work_capacity", work_capacity, cluster_work_doubles(n_frames, d, k), "partial sums", "doubles");
     if (!y_dev || !labels_dev || !counts_dev || !sums_dev || !work_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
@@ -402,7 +386,7 @@ int jamun_swd_project(const float* x_dev, int64_t row_stride, int32_t n_frames, 
     check_range("n_frames", n_frames, 1, INT32_MAX);
     check_range("width", width, 1, JAMUN_SWD_MAX_WIDTH);
     check_range("n_proj", n_proj, 1, JAMUN_SWD_MAX_PROJ);
-    if (row_stride < width) throw Err(JAMUN_ERR_INVALID, "row_stride " + std::to_string(row_stride) + " is below the width " + std::to_string(width));
+    check_row_stride(row_stride, width, "the width ");
     require_capacity("out_capacity", out_capacity, (int64_t)n_frames * n_proj, "keys", "floats");
     if (!x_dev || !proj_dev || !out_dev) throw Err(JAMUN_ERR_INVALID, "null argument");
     launch_swd_project(x_dev, row_stride, n_frames, width, proj_dev, n_proj, out_dev, (hipStream_t)stream);

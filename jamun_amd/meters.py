@@ -1,5 +1,5 @@
-"""What the per-trajectory meters (`ramachandran.RamachandranMetrics`, `validity.ChemicalValidityMetrics`, `tica.TICAMetrics`, `msm.MSMMetrics`) share: the ``TrajectoryMetric``
-protocol `callbacks.TrajectoryMetricCallback` drives, the choice between the device and the host path, the reference frames, the view of a
+"""What the five per-trajectory meters (`ramachandran.RamachandranMetrics`, `validity.ChemicalValidityMetrics`, `tica.TICAMetrics`,
+`msm.MSMMetrics`, `swd.SlicedWassersteinMetrics`) share: the ``TrajectoryMetric`` protocol `callbacks.TrajectoryMetricCallback` drives, the choice between the device and the host path, the reference frames, the view of a
 chain, and the reproducible ``.npz`` writer.  A meter derives from `TrajectoryMeter`, names its directory and its device condition, and
 keeps its own tables, ``on_sample_start``, the body of ``update`` and ``compute``."""
 

@@ -245,6 +245,48 @@ def test_the_c_entries_refuse_bad_arguments_and_write_nothing():
         assert intact(big, fill)
 
 
+def test_the_count_bindings_refuse_what_only_labels_on_a_gpu_let_them_reach():
+    """`native.transition_counts` and `native.label_counts` check their labels first, and those must be on a GPU: the refusals behind that
+    check (``lag``, ``n_states``, ``state_map``, ``bounds``, the segment count, ``out=``), their texts and which of two faults is reported.
+    Every call is refused on the host: nothing is launched."""
+    import re
+
+    from jamun_amd import native
+
+    dev = _dev()
+    T = 20
+    labels = torch.zeros(T, dtype=torch.int32, device=dev)
+
+    def refused(kind, text, fn, *args, **kwargs):
+        with pytest.raises(kind, match="^" + re.escape(text) + "$"):
+            fn(*args, **kwargs)
+
+    for lag in (0, -2, 1.0, True, "1"):
+        refused(ValueError, f"lag must be an integer of at least 1, got {lag!r}", native.transition_counts, labels, lag, 4)
+    refused(RuntimeError, "lag must fit 31 bits", native.transition_counts, labels, 2**31, 4)
+    refused(RuntimeError, f"labels must be a contiguous int32 [frames] tensor on the GPU, got torch.int64 ({T},) on {dev}",
+            native.transition_counts, labels.long(), 0, 0)  # (labels, then lag)
+    refused(ValueError, "lag must be an integer of at least 1, got 0", native.transition_counts, labels, 0, 0)  # (lag, then n_states)
+    for fn, mid in ((native.transition_counts, 1), (native.label_counts, [0, T])):
+        for n_states in (0, 1025, 4.0, False):
+            refused(ValueError, f"n_states must be an integer in [1, 1024], got {n_states!r}", fn, labels, mid, n_states)
+        refused(ValueError, "state_map must be a non-empty int32 [n_in] table, got torch.int64 (3,)", fn, labels, mid, 4,
+                state_map=torch.zeros(3, dtype=torch.int64, device=dev))
+        refused(ValueError, "state_map must be a non-empty int32 [n_in] table, got torch.int32 (0,)", fn, labels, mid, 4, state_map=[])
+    refused(RuntimeError, f"out must be a contiguous int64 [4, 4] tensor on {dev}, got torch.int32 (4, 4) on {dev}", native.transition_counts, labels, 1, 4,
+            out=torch.zeros(4, 4, dtype=torch.int32, device=dev))
+    for bounds, shown in (([0], "[0]"), ([5, 3], "[5, 3]"), ([0, T + 1], f"[0, {T + 1}]"), ([-1, 5], "[-1, 5]"), ([0.0, 5.0], "[0.0, 5.0]"),
+                          ([[0, 5]], "[[0, 5]]"), (np.arange(17)[::-1], "(17,)")):
+        refused(ValueError, f"bounds must be at least two non-decreasing integers within [0, {T}], got {shown}", native.label_counts, labels, bounds, 4)
+    refused(ValueError, "n_states must be an integer in [1, 1024], got 0", native.label_counts, labels, [5, 3], 0)  # (n_states, then bounds)
+    refused(ValueError, f"bounds on the device must be a contiguous int32 [n_seg + 1] tensor on {dev}, got torch.int64 (3,) on {dev}",
+            native.label_counts, labels, torch.tensor([0, 5, T], device=dev), 4)
+    refused(ValueError, "4097 segments: the device path takes 1 to 4096", native.label_counts, labels, np.zeros(4098, np.int64), 4)
+    refused(ValueError, "0 segments: the device path takes 1 to 4096", native.label_counts, labels, torch.zeros(1, dtype=torch.int32, device=dev), 4)
+    refused(RuntimeError, f"out must be a contiguous int64 [2, 4] tensor on {dev}, got torch.int64 (4, 2) on {dev}", native.label_counts, labels, [0, 5, T], 4,
+            out=torch.zeros(4, 2, dtype=torch.int64, device=dev))
+
+
 @pytest.mark.parametrize("T,d,k", [(2049, 2, 8), (1500, 17, 65)])
 def test_kmeans_on_the_device_gives_the_hosts_centres_bit_for_bit(T, d, k):
     dev = _dev()

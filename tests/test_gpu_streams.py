@@ -367,7 +367,7 @@ def test_a_sampler_walks_while_the_previous_trajectory_is_analysed_on_a_side_str
 
 
 def test_lagged_moments_on_two_streams_keep_their_partial_sums_apart(busy):
-    """`native._tica_workspace`: one workspace per (device, stream).  Two calls on different inputs at once, then the same pair with more
+    """`native._workspace`: one workspace per (device, stream).  Two calls on different inputs at once, then the same pair with more
     frames, so that both workspaces are replaced while the first pair may still be running."""
     from jamun_amd import native
 
@@ -387,12 +387,12 @@ def test_lagged_moments_on_two_streams_keep_their_partial_sums_apart(busy):
         with torch.cuda.stream(streams[i]):
             busy(i, BUSY_STEPS // 4)
             got[i] = [o.clone() for o in native.lagged_moments(small[i], 5)]
-    sizes = [native._tica_work[str(dev), int(s.cuda_stream)].numel() for s in streams]
+    sizes = [native._work[str(dev), int(s.cuda_stream)].numel() for s in streams]
     for i in (0, 1):
         with torch.cuda.stream(streams[i]):
             got[2 + i] = [o.clone() for o in native.lagged_moments(large[i], 5)]
-    assert all(native._tica_work[str(dev), int(s.cuda_stream)].numel() > n for s, n in zip(streams, sizes))  # (both grew)
-    assert native._tica_work[str(dev), int(streams[0].cuda_stream)].data_ptr() != native._tica_work[str(dev), int(streams[1].cuda_stream)].data_ptr()
+    assert all(native._work[str(dev), int(s.cuda_stream)].numel() > n for s, n in zip(streams, sizes))  # (both grew)
+    assert native._work[str(dev), int(streams[0].cuda_stream)].data_ptr() != native._work[str(dev), int(streams[1].cuda_stream)].data_ptr()
     for s in streams:
         s.synchronize()
     for i in range(4):
