@@ -265,7 +265,7 @@ def test_callback_device_path_writes_the_host_path_torsions(tmp_path, monkeypatc
     assert len(tors) == 2 * chains + 2
     assert {f: d for f, d in trees["device"].items() if "torsion" not in f} == trees["raw"]  # byte for byte the run without the option
     assert trees["device"][os.path.join("m", "torsion_labels.json")] == trees["host"][os.path.join("m", "torsion_labels.json")]
-    index = cbs["device"]._tor_index["m"]
+    index = cbs["device"]._states["m"].tor_index
     assert index.shape == (3, 4)
     d, h = (tmp_path / m / "m" / "predicted_samples" / "torsions" for m in ("device", "host"))
     for name in [str(i) for i in range(2 * chains)] + ["joined"]:

@@ -1,6 +1,7 @@
 """GPU tests of the trajectory encoders (jamun_traj.hip) and of ``SaveTrajectoryCallback(encode="device")``.  The expected bytes always
 come from `pdb.save_pdb` / `pdb.save_dcd` (MODEL lines renumbered for a late ``first_model``), never from the encoder."""
 import filecmp
+import json
 import os
 import re
 import time
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import _trajectory_device_case as case
 from _frames_common import _dev
 from _traj_molecules import molecule, named_chain
 
@@ -209,17 +211,17 @@ def _trees_equal(a: str, b: str) -> int:
     return len(fa)
 
 
-def _run_both(tmp_path, batches, datasets, dev, **kw):
+def _run_both(tmp_path, batches, datasets, dev, modes=("device", "host"), **kw):
     from jamun_amd.callbacks import SaveTrajectoryCallback
 
-    cbs = {m: SaveTrajectoryCallback(datasets, output_dir=str(tmp_path / m), encode=m, **kw) for m in ("device", "host")}
+    cbs = {m: SaveTrajectoryCallback(datasets, output_dir=str(tmp_path / m), encode=m, **kw) for m in modes}
     for cb in cbs.values():
         cb.on_sample_start(_GpuSampler(dev))
     for b in batches:
         for cb in cbs.values():
             cb.on_after_sample_batch(b, _GpuSampler(dev))
             cb.flush()
-        n_files = _trees_equal(str(tmp_path / "device"), str(tmp_path / "host"))  # after EVERY batch
+        n_files = _trees_equal(str(tmp_path / modes[0]), str(tmp_path / modes[1]))  # after EVERY batch
     for cb in cbs.values():
         cb.on_sample_end(_GpuSampler(dev))
     return cbs, n_files
@@ -260,6 +262,47 @@ def test_callback_rewrites_files_with_unencodable_values_on_the_host_path(tmp_pa
     _run_both(tmp_path, batches, [_DS(a, "a")], dev)
     txt = open(str(tmp_path / "device" / "a" / "predicted_samples" / "pdb" / "joined.pdb")).read()
     assert "     nan" in txt and "10000.000" in txt and "     inf" in txt
+
+
+def test_host_batch_then_device_batches_write_the_host_tree(tmp_path):
+    """``encode="auto"``: batch 1 arrives as CPU tensors (host path), batches 2 and 3 on the GPU, which extend ``joined.*`` behind files the
+    host path wrote; batch 2 carries values no PDB field holds, so its files and ``joined.pdb`` are rewritten by the host formatter."""
+    dev = _dev()
+    a = molecule(10)
+    walkers = [(a, "a")] * 3
+
+    def poke(traj):
+        traj[2, 13, 1] = float("nan")
+        traj[5, 25, 0] = 1000.0
+        traj[6, 25, 2] = float("inf")
+
+    batches = [_batch(walkers, 9, torch.device("cpu"), seed=0), _batch(walkers, 9, dev, seed=1, poke=poke), _batch(walkers, 9, dev, seed=2)]
+    cbs, n_files = _run_both(tmp_path, batches, [_DS(a, "a")], dev, modes=("auto", "host"))
+    assert n_files == 1 + 3 * (3 * 3 + 1)
+    assert cbs["auto"]._encoder is not None and cbs["host"]._encoder is None and not cbs["auto"]._dev_blocks
+    txt = open(str(tmp_path / "auto" / "a" / "predicted_samples" / "pdb" / "joined.pdb")).read()
+    assert "     nan" in txt and "10000.000" in txt and "     inf" in txt and txt.count("MODEL ") == 3 * 3 * 9
+
+
+@pytest.mark.parametrize("staging", [case.STAGING_64K, None], ids=["staging_64k", "staging_default"])
+def test_all_options_device_tree_has_the_recorded_digests(tmp_path, monkeypatch, golden_dir, staging):
+    """_trajectory_device_case.py: superposition, torsions, PDB and DCD of two labels at once.  With 64 KiB of staging a 166-atom chain is
+    two aligned spans (32 + 8 frames), each several PDB chunks and one DCD chunk; with the default size everything is one chunk, and the
+    bytes are the same: one set of digests, recorded before the writer was split into steps."""
+    from jamun_amd import traj_encode
+
+    if staging is not None:
+        monkeypatch.setattr(traj_encode, "STAGING_BYTES", staging)
+        n = 166
+        assert traj_encode.DeviceTrajectoryEncoder.align_frames_per_chunk(n) == traj_encode.DeviceTrajectoryEncoder.dcd_frames_per_chunk(n) == 32
+    with open(os.path.join(golden_dir, "trajectory_device_trees.json")) as f:
+        want = json.load(f)
+    for label in ("m", "c"):  # the recorded set covers every encoded file of both labels
+        for ext in ("pdb", "dcd"):
+            assert all(f"{label}/predicted_samples/{ext}/{i}.{ext}" in want for i in (list(range(6 if label == "m" else 3)) + ["joined"]))
+    got = case.digests(str(tmp_path / "out"), _dev())
+    assert sorted(f for f in want if f not in got) == []
+    assert sorted(f for f in want if got[f] != want[f]) == []
 
 
 def test_staging_memory_is_constant(tmp_path):
