@@ -465,6 +465,40 @@ int jamun_swd_w2sq_work(int32_t n, int32_t m, int32_t n_proj, int64_t* n_doubles
 int jamun_swd_w2sq(const float* u_dev, int64_t u_stride, int32_t n, const float* v_dev, int64_t v_stride, int32_t m, int32_t n_proj, double* out_dev,
                    double* work_dev, int64_t work_capacity, void* stream);
 
+/* ---- denoising evaluation: the two ends of Denoiser.noise_and_denoise / compute_loss around the forward -----------------------------------
+ * (src/jamun/model/denoiser.py:219-297, utils/align.py:9-56.)  A ragged batch of n_graphs graphs and n_atoms atoms: ptr_dev [n_graphs + 1]
+ * int32 on the device, the atoms of graph g are ptr[g] .. ptr[g + 1] - 1, as jamun_mean_center takes it.  The kernels clamp the table to
+ * [0, n_atoms], so a table that does not ascend from 0 to n_atoms gives values that mean nothing but never an access outside the buffers.
+ * One workgroup per graph, fp32, every product and sum rounded on its own, every sum in a fixed order: the same inputs give the same bits
+ * in every run.  No floating-point atomics.
+ *
+ * jamun_noise_align_graphs   x_dev, noise_dev [n_atoms, 3] -> x_c_dev, y_dev [n_atoms, 3], rmsd_dev [n_graphs] (may be NULL):
+ *     x_c = x - centroid(x)                      only if mean_center != 0, else x_c = x
+ *     y   = x_c + sigma * noise
+ *     y  -= centroid(y)                          only if mean_center != 0
+ *     y   = R (y - c_y) + c_x                    only if align != 0: c_y, c_x the centroids of y and x_c, R the PROPER rotation (det +1, never
+ *                                                a reflection) that minimises sum_i |R (y_i - c_y) + c_x - x_c,i|^2
+ *     rmsd[g] = sqrt(mean_i |y_i - x_c,i|^2)     of the values written
+ *   Every centroid is the sequential fp32 sum in atom order divided by the count: x_c holds the bits of jamun_mean_center(x), and without
+ *   align y those of the same fp32 operations done on a host.  R is the top eigenvector of Horn's quaternion matrix of the covariance of the
+ *   centred coordinates (cyclic Jacobi sweeps, as jamun_superpose_frames): graphs of one or two atoms or of collinear atoms get some optimal
+ *   rotation and finite values, the mirror image of x gets the best rotation with rmsd > 0.  A graph with a non-finite value gets a
+ *   non-finite y and leaves every other graph alone; a graph without atoms writes nothing (rmsd[g] included).  x_c_dev may be x_dev.
+ *
+ * jamun_denoise_loss   xhat_dev, x_c_dev [n_atoms, 3], loss_weight_dev [n_graphs] (NULL: ones) -> out_dev [n_graphs, 3]:
+ *     out[g][0] = raw_coordinate_loss = mean_i |xhat_i - x_i|^2
+ *     out[g][1] = scaled_rmsd         = mean_i |xhat_i - x_i| / (sigma * sqrt(3))
+ *     out[g][2] = coordinate_loss     = out[g][0] * loss_weight[g] * inv_c_out_sq
+ *   The per-atom terms of a graph are added in atom order in fp32, as scatter_mean adds them on the CPU; a graph without atoms gives zeros.
+ *
+ * A NULL pointer that is needed, a negative count, sigma that is not finite or not above 0, 3 n_atoms beyond 31 bits or a ptr_dev that is
+ * not device memory is JAMUN_ERR_INVALID and nothing is written; n_graphs == 0 launches nothing.  Caller-owned buffers, work queued on
+ * `stream`, no synchronisation, no allocation, nothing read back. */
+int jamun_noise_align_graphs(const float* x_dev, const float* noise_dev, const int32_t* ptr_dev, int32_t n_graphs, int32_t n_atoms, float sigma,
+                             int32_t mean_center, int32_t align, float* x_c_dev, float* y_dev, float* rmsd_dev, void* stream);
+int jamun_denoise_loss(const float* xhat_dev, const float* x_c_dev, const int32_t* ptr_dev, int32_t n_graphs, int32_t n_atoms, float sigma,
+                       const float* loss_weight_dev, float inv_c_out_sq, float* out_dev, void* stream);
+
 /* The graph half of a forward on its own: Denoiser.add_edges + the edge geometry + the radial MLPs' hidden layer
  * (src/jamun/model/denoiser.py:138-166, arch/e3conv.py:110-127, e3tools/nn/_conv.py:112) for positions y_dev [n_atoms,3]; the
  * result stays inside the sampler as the edge table the blocks below run on. */

@@ -145,6 +145,8 @@ SYMBOLS = {
     "jamun_swd_merge": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "jamun_swd_w2sq_work": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "jamun_swd_w2sq": (C.c_int, [_P, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "jamun_noise_align_graphs": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "jamun_denoise_loss": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_float, _P, C.c_float, _P, _P]),
     "jamun_build_edges": (C.c_int, [_P, _P, _P]),
     "jamun_conv_block": (C.c_int, [_P, C.c_int32, _P, _P, _P]),
     "jamun_sampler_stats": (C.c_int, [_P, C.POINTER(jamun_stats), _P]),

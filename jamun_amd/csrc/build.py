@@ -20,7 +20,7 @@ ROOT = os.path.dirname(PKG)
 OUT = os.path.join(PKG, "libjamun_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 SOURCES = ["jamun_kernels.hip", "jamun_conv.hip", "jamun_conv_initv.hip", "jamun_conv_dg.hip", "jamun_tprod.hip", "jamun_conv_mf.hip", "jamun_conv_tail.hip", "jamun_conv_ml.hip",
-           "jamun_node.hip", "jamun_sepconv.hip", "jamun_wide.hip", "jamun_traj.hip", "jamun_superpose.hip", "jamun_intcoord.hip", "jamun_hist.hip", "jamun_validity.hip", "jamun_tica.hip", "jamun_msm.hip", "jamun_swd.hip", "jamun_api.cpp", "jamun_frames.cpp", "jamun_pack.cpp", "jamun_plan.cpp"]
+           "jamun_node.hip", "jamun_sepconv.hip", "jamun_wide.hip", "jamun_traj.hip", "jamun_superpose.hip", "jamun_intcoord.hip", "jamun_hist.hip", "jamun_validity.hip", "jamun_tica.hip", "jamun_msm.hip", "jamun_swd.hip", "jamun_denoise.hip", "jamun_api.cpp", "jamun_frames.cpp", "jamun_denoise.cpp", "jamun_pack.cpp", "jamun_plan.cpp"]
 HEADERS = ["jamun_internal.h", "jamun_host.h", "jamun_conv_form.h", "jamun_conv_mf_layout.h", "jamun_dev.h", "jamun_split.h", os.path.join(ROOT, "include", "jamun_hip.h")]
 DEPS = SOURCES + HEADERS
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -54,11 +54,11 @@ def _obj_digest(src: str) -> str:
 
 
 def _compile(src: str, verbose: bool) -> str:
-    obj = os.path.join(OBJ_DIR, f"{os.path.splitext(src)[0]}.{_obj_digest(src)}.o")
+    obj = os.path.join(OBJ_DIR, f"{src}.{_obj_digest(src)}.o")  # (the whole file name: jamun_denoise.hip and jamun_denoise.cpp share a stem)
     if os.path.exists(obj):
         return obj
     for old in os.listdir(OBJ_DIR):  # objects of older versions of this source
-        if old.startswith(os.path.splitext(src)[0] + ".") and old.endswith(".o"):
+        if old.startswith(src + ".") and old.endswith(".o"):
             os.unlink(os.path.join(OBJ_DIR, old))
     tmp = obj + f".tmp{os.getpid()}"
     cmd = [HIPCC] + CFLAGS + EXTRA + ["-c", os.path.join(HERE, src), "-o", tmp]

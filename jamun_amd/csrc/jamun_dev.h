@@ -1,5 +1,6 @@
 // jamun_dev.h — THE device helpers of every kernel file of the library (one definition each): the vector typedefs, the MFMA wrappers, the
-// f16x3 product macros, readfirstlane, the LDS barrier, absolute-address LDS accesses and constant address-space loads, power-of-two scales.
+// f16x3 product macros, readfirstlane, the LDS barrier, absolute-address LDS accesses and constant address-space loads, power-of-two scales, the Jacobi rotation of the 4x4 eigen-solvers
+// (jamun_superpose.hip, jamun_denoise.hip).
 // The f16x3 split primitives themselves are jamun_split.h (included here).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -92,5 +93,39 @@ __device__ __forceinline__ float pow2f(int e) { return __uint_as_float((unsigned
 __device__ __forceinline__ int exp_above(float v) { return (int)((__float_as_uint(v) >> 23) & 0xffu) - 126; }  // v < 2^exp_above(v)
 __device__ __forceinline__ int clamp40(int s) { return max(-40, min(40, s)); }
 __device__ __forceinline__ int clamp100(int s) { return max(-100, min(100, s)); }
+
+// One Jacobi rotation in the (p, q) plane of the symmetric 4x4 matrix held as scalars: app, aqq, apq and the two other rows' entries
+// (arp, arq), (asp, asq); v*p / v*q are columns p and q of the accumulated eigenvector matrix.  t = tan of the rotation angle, the smaller
+// root (|t| <= 1); apq == 0 leaves everything as it is (t = 0) without a branch that diverges.
+__device__ __forceinline__ void jacobi_rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float& asp, float& asq, float& v0p, float& v0q,
+                                              float& v1p, float& v1q, float& v2p, float& v2q, float& v3p, float& v3q) {
+  const float theta = (aqq - app) / (2.0f * apq);
+  const float root = sqrtf(theta * theta + 1.0f);  // (theta * theta may overflow to inf: t = 0, the right limit)
+  float t = (theta < 0.0f ? -1.0f : 1.0f) / (fabsf(theta) + root);
+  t = apq == 0.0f ? 0.0f : t;
+  const float c = 1.0f / sqrtf(t * t + 1.0f);
+  const float s = t * c;
+  app = app - t * apq;
+  aqq = aqq + t * apq;
+  apq = 0.0f;
+  float x = arp, y = arq;
+  arp = c * x - s * y;
+  arq = s * x + c * y;
+  x = asp, y = asq;
+  asp = c * x - s * y;
+  asq = s * x + c * y;
+  x = v0p, y = v0q;
+  v0p = c * x - s * y;
+  v0q = s * x + c * y;
+  x = v1p, y = v1q;
+  v1p = c * x - s * y;
+  v1q = s * x + c * y;
+  x = v2p, y = v2q;
+  v2p = c * x - s * y;
+  v2q = s * x + c * y;
+  x = v3p, y = v3q;
+  v3p = c * x - s * y;
+  v3q = s * x + c * y;
+}
 
 }  // namespace

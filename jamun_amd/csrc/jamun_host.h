@@ -1,5 +1,6 @@
 // jamun_host.h — host-only declarations shared by jamun_pack.cpp (weight packing), jamun_plan.cpp (tile / work-list planning and
-// kernel selection), jamun_api.cpp (sampler create, dispatch, the C ABI) and jamun_frames.cpp (the C entries on frames).  Not included
+// kernel selection), jamun_api.cpp (sampler create, dispatch, the C ABI), jamun_frames.cpp (the C entries on frames) and jamun_denoise.cpp
+// (the C entries of the denoising evaluation).  Not included
 // by any .hip file.
 #pragma once
 #include <hip/hip_runtime.h>

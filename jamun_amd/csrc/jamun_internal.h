@@ -510,6 +510,12 @@ void launch_encode_dcd(const float* xyz, long long frame_stride, long long atom_
 // jamun_superpose.hip — rigid superposition of frames on a reference structure, per-frame RMSD
 void launch_superpose_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* ref, float* out,
                              long long out_frame_stride, long long out_atom_stride, float* rmsd, hipStream_t st);
+// jamun_denoise.hip — the two ends of a denoising evaluation on a ragged batch (ptr [n_graphs + 1], clamped to [0, n_atoms] by the kernels): noise,
+// centre and align clean frames; per-graph losses of denoised frames.  n_graphs >= 1; rmsd and loss_weight may be null
+void launch_noise_align(const float* x, const float* noise, const int* ptr, int n_graphs, int n_atoms, float sigma, int mean_center, int align, float* x_c,
+                        float* y, float* rmsd, hipStream_t st);
+void launch_denoise_loss(const float* xhat, const float* x_c, const int* ptr, int n_graphs, int n_atoms, float rmsd_scale, const float* loss_weight,
+                         float inv_c_out_sq, float* out, hipStream_t st);
 // jamun_intcoord.hip — internal coordinates of frames (distances, bond angles, dihedrals) from an index table; n_frames, n_feat >= 1
 #define JAMUN_INTCOORD_FTILE 16  // table rows a workgroup stages at a time (native.INTCOORD_FEATURE_TILE mirrors it for the tests)
 void launch_internal_coords(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const int* idx, int n_feat,

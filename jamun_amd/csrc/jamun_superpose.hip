@@ -30,46 +30,13 @@
 #include <stdint.h>
 
 #include "jamun_internal.h"
+#include "jamun_dev.h"
 
 namespace {
 
 constexpr int SP_THREADS = 64;   // one wave per workgroup
 constexpr int SP_TILE = 256;     // reference atoms staged in LDS at a time (3 KiB: LDS never bounds the waves per CU)
-constexpr int SP_SWEEPS = 6;     // cyclic Jacobi sweeps of the 4x4 matrix: fp32 converges in 4 (quadratically); 6 leaves margin for near-degenerate pairs
-
-// One Jacobi rotation in the (p, q) plane of the symmetric 4x4 matrix held as scalars: app, aqq, apq and the two other rows' entries
-// (arp, arq), (asp, asq); v*p / v*q are columns p and q of the accumulated eigenvector matrix.  t = tan of the rotation angle, the smaller
-// root (|t| <= 1); apq == 0 leaves everything as it is (t = 0) without a branch that diverges.
-__device__ __forceinline__ void jacobi_rotate(float& app, float& aqq, float& apq, float& arp, float& arq, float& asp, float& asq, float& v0p, float& v0q,
-                                              float& v1p, float& v1q, float& v2p, float& v2q, float& v3p, float& v3q) {
-  const float theta = (aqq - app) / (2.0f * apq);
-  const float root = sqrtf(theta * theta + 1.0f);  // (theta * theta may overflow to inf: t = 0, the right limit)
-  float t = (theta < 0.0f ? -1.0f : 1.0f) / (fabsf(theta) + root);
-  t = apq == 0.0f ? 0.0f : t;
-  const float c = 1.0f / sqrtf(t * t + 1.0f);
-  const float s = t * c;
-  app = app - t * apq;
-  aqq = aqq + t * apq;
-  apq = 0.0f;
-  float x = arp, y = arq;
-  arp = c * x - s * y;
-  arq = s * x + c * y;
-  x = asp, y = asq;
-  asp = c * x - s * y;
-  asq = s * x + c * y;
-  x = v0p, y = v0q;
-  v0p = c * x - s * y;
-  v0q = s * x + c * y;
-  x = v1p, y = v1q;
-  v1p = c * x - s * y;
-  v1q = s * x + c * y;
-  x = v2p, y = v2q;
-  v2p = c * x - s * y;
-  v2q = s * x + c * y;
-  x = v3p, y = v3q;
-  v3p = c * x - s * y;
-  v3q = s * x + c * y;
-}
+constexpr int SP_SWEEPS = 6;     // cyclic Jacobi sweeps (jacobi_rotate, jamun_dev.h) of the 4x4 matrix: fp32 converges in 4 (quadratically); 6 leaves margin for near-degenerate pairs
 
 __global__ void __launch_bounds__(SP_THREADS)
 k_superpose_frames(const float* xyz, long long frame_stride, long long atom_stride, int n_atoms, int n_frames, const float* __restrict__ ref,

@@ -1,6 +1,7 @@
 """Thin object wrappers over the C ABI (``include/jamun_hip.h``): model / sampler handles and the stand-alone operators (the entries of
 ``csrc/jamun_api.cpp``).  The calls that encode or analyse frames of a trajectory (``csrc/jamun_frames.cpp``) live in `native_frames`;
-their public names are handed out here as well, so ``native.superpose_frames`` and the rest keep working.
+their public names are handed out here as well, so ``native.superpose_frames`` and the rest keep working; the two ends of a denoising
+evaluation (``csrc/jamun_denoise.cpp``) live in `native_denoise` and are handed out here too.
 
 PyTorch is used only for device memory and streams: every call passes ``tensor.data_ptr()`` and
 ``torch.cuda.current_stream().cuda_stream`` to the HIP library.
@@ -26,6 +27,7 @@ from .native_frames import (  # noqa: F401 (every public name it defines)
     MSM_MAX_SEGMENTS, check_centers_shape, assign_centers, cluster_sums, transition_counts, label_counts, SWD_TILE, SWD_MAX_WIDTH, SWD_MAX_PROJ,
     check_swd_shapes, swd_project, swd_sort_segments, swd_merge, swd_w2sq,
 )
+from .native_denoise import noise_align_graphs, denoise_loss, noise_align_graphs_host, denoise_loss_host  # noqa: F401
 from .native_frames import _ptr, _result, _state_map, _stream, _table, _work, _workspace  # noqa: F401 (all but _ptr, _stream: tests reach them here)
 
 
